@@ -18,11 +18,19 @@
            the 128-byte RCCL id to the ranks and the barriers around the timed region.
            Weak scaling: N x 1M points per cloud.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with extra objects:
-"roofline" (correspondence kernel vs the HBM roof), "cpu_baseline" (the CPU oracle timed on
-this box's host cores: 1 core, and the MultiMatcher pattern on all usable cores) and
-"other_configs" (BASELINE configs[2] GICP 500k, configs[3] NDT 2M, configs[0] 10k pairs in
-batches of 256, and default-parameter matches of 55k pairs in batches of 128) -- N == 1 only.
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step, ... and "roofline"
+(correspondence kernel vs the HBM roof, from the timed steps' event-bracketed launches and the committed counter capture).
+A plain run sets up, warms up, times --steps registrations and prints that line.
+
+--full adds every other measurement, each a run of its own after the timed steps: "config.host_clouds"
+(the step from pageable / pinned host clouds), "in_flight" (several registrations in flight),
+"other_configs" (BASELINE configs[2] GICP 500k, configs[3] NDT 2M, configs[0] 10k pairs in batches of
+256, and default-parameter matches of 55k pairs in batches of 128), "cpu_baseline" (the CPU oracle timed
+on this box's host cores: 1 core, and the MultiMatcher pattern on all usable cores) -- N == 1 only --,
+the device's copy rate (roofline.hbm_util) and, at N > 1, the isolated all-reduce and the second timing
+with the collective exchange.  The --no-* options leave single parts of --full out.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64 / float32).
 """
 import argparse
 import json
@@ -54,18 +62,53 @@ F64_VALU_PEAK_TFLOPS = 78.6  # MI355X vector FP64 (half the 157.3 TFLOP/s FP32 v
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed registrations")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", type=int, default=1_000_000, help="points per cloud PER GPU")
     ap.add_argument("--iters", type=int, default=50, help="forced ICP iterations per registration")
     ap.add_argument("--max-corr", type=float, default=3.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-in-flight", action="store_true", help="skip the several-registrations-in-flight measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other measurement too (host clouds, registrations in flight, "
+                         "other configs, CPU baselines, the device's copy rate; at N > 1 the collective exchange)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other configs")
+    ap.add_argument("--no-in-flight", action="store_true",
+                    help="with --full: skip the several-registrations-in-flight measurement")
     ap.add_argument("--no-host-clouds", action="store_true",
-                    help="skip the H2D-inclusive steps (counter captures: the process then ends with the timed registrations)")
+                    help="with --full: skip the H2D-inclusive steps (counter captures: the process then ends with the timed registrations)")
     ap.add_argument("--cpu-iters", type=int, default=20, help="oracle iterations timed for the baseline")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_MAX_POINTS = 2_000_000  # per-point outputs above this are dumped as a fixed, seeded sample (at most 20 B a point)
+
+
+def dump_outputs(out_dir, r, ctx=None):
+    """What the last timed step computed, as `out_dir`/<name>.npy: the registration's transform and the statistics
+    wm_icp_align returns (float64) and, from a single-GPU context, the last iteration's correspondences -- matched
+    target index (float64, -1 = none) and squared distance (float32) per source point, in source order.  Clouds of
+    more than DUMP_MAX_POINTS points leave a sample of that many source points (seed 0, ascending; indices in
+    correspondence_sample.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"transform": np.asarray(r["T"], dtype=np.float64)}
+    for k in ("iterations", "n_corr", "mse", "prev_mse", "converged"):
+        arrays[k] = np.asarray(float(r[k]), dtype=np.float64)
+    if ctx is not None:
+        idx, d2 = ctx.correspondences()
+        if len(idx) > DUMP_MAX_POINTS:
+            pick = np.sort(np.random.default_rng(0).choice(len(idx), DUMP_MAX_POINTS, replace=False))
+            idx, d2 = idx[pick], d2[pick]
+            arrays["correspondence_sample"] = pick.astype(np.float64)
+        arrays["correspondence_index"] = idx.astype(np.float64)
+        arrays["correspondence_d2"] = d2.astype(np.float32)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return sorted(arrays)
 
 
 def first_step_with_fallback(step, rebuild, all_ranks_ok, error_type):
@@ -892,17 +935,17 @@ def main():
     # ones, profiles/r05m_bench_line_noprof.json; the interpreter's collector is the one pause this script can rule
     # out.  Collected BEFORE the warm-up: a collection between warm-up and timing leaves the GPU idle for tens of
     # milliseconds and the first timed step 0.3 ms slower, gpurun_out/r05n_jitter)
-    # (the device's copy rate -- what `roofline.hbm_util` is a fraction of -- is measured BEFORE the registrations: it is the
-    # bench's one other device-wide measurement, and a device that has just moved 40 GB enters the warm-up at its working
-    # clocks rather than from idle)
-    peak_copy_early = ctx.copy_bandwidth() if (world == 1 and rank == 0) else None
+    # (--full: the device's copy rate -- what `roofline.hbm_util` is a fraction of -- is measured BEFORE the registrations:
+    # it is the bench's one other device-wide measurement, and a device that has just moved 40 GB enters the warm-up at
+    # its working clocks rather than from idle)
+    peak_copy_early = ctx.copy_bandwidth() if (a.full and world == 1 and rank == 0) else None
     import gc
     gc.collect()
     gc.disable()
     for _ in range(a.warmup):
         r = step(1)
     torch.cuda.synchronize()
-    ar_us = ctx.allreduce_probe(comm) if comm is not None else None
+    ar_us = ctx.allreduce_probe(comm) if (a.full and comm is not None) else None
     if dist:
         dist.barrier()
     t0 = time.perf_counter()
@@ -934,12 +977,16 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # (before anything else runs on the context: the correspondences are the last timed step's)
+        dump_outputs(a.dump_outputs, r, ctx if dist is None else None)
 
-    # N > 1 (or the one-rank plumbing check): north_star names "RCCL all-reduce over xGMI" as the exchange, the library's
-    # default is its own mailbox exchange inside the solve kernel.  When mailboxes ran, the SAME registration is timed
-    # once more, shortly, with the group rebuilt on ncclAllReduce (WM_COMM_P2P=0): the line carries both.
+    # N > 1 (or the one-rank plumbing check), --full: north_star names "RCCL all-reduce over xGMI" as the exchange, the
+    # library's default is its own mailbox exchange inside the solve kernel.  When mailboxes ran, the SAME registration is
+    # timed once more, shortly, with the group rebuilt on ncclAllReduce (WM_COMM_P2P=0): the line carries both.
     other_exchange = None
-    if comm is not None and not exchange_fallback and bool(r.get("exchange_in_kernel")) and os.environ.get("WM_COMM_P2P", "1") != "0":
+    if (a.full and comm is not None and not exchange_fallback and bool(r.get("exchange_in_kernel"))
+            and os.environ.get("WM_COMM_P2P", "1") != "0"):
         try:
             rebuild_collective()
             ctx, comm = box["ctx"], box["comm"]
@@ -978,7 +1025,7 @@ def main():
                     out["config"]["ms_per_step_mailbox_exchange"] = elapsed / a.steps * 1e3
                     out["config"]["ms_per_step_rccl_allreduce_exchange"] = other_exchange["ms_per_step"]
         value = out["value"]
-        if world == 1 and dist is None and not a.no_host_clouds:
+        if a.full and world == 1 and dist is None and not a.no_host_clouds:
             # the same registration from HOST clouds: H2D of both clouds inside the step
             hc = {}
             for name, (hr, ht) in (("pageable", (ref, tgt)),
@@ -1004,7 +1051,7 @@ def main():
             out["value_h2d_inclusive"] = hc["pinned"]["registrations_per_s"]
             out["value_h2d_inclusive_note"] = ("the same registration from pinned HOST clouds (both uploads inside the "
                                                "timed step); `value` is with the clouds already in HBM")
-        if world == 1 and dist is None and not a.no_in_flight:
+        if a.full and world == 1 and dist is None and not a.no_in_flight:
             # configs[1] with MORE THAN ONE registration in flight (the headline `value` stays one at a time)
             try:
                 pin_r, pin_t = torch.from_numpy(ref).pin_memory().numpy(), torch.from_numpy(tgt).pin_memory().numpy()
@@ -1017,9 +1064,9 @@ def main():
                         out["config"]["registrations_per_s_%d_in_flight%s" % (row["workers"], suffix)] = row["registrations_per_s"]
             except Exception as ex:  # (never lose the line over the extra measurement)
                 out["in_flight"] = {"error": str(ex)}
-        if world == 1 and not a.no_other_configs:
+        if a.full and world == 1 and not a.no_other_configs:
             out["other_configs"] = other_configs(torch, dev, capi, synth, pmc, not a.no_cpu_baseline, peak_copy)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(ref, tgt, a.iters, a.max_corr, a.cpu_iters)
             out["config"]["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
             if "all_cores" in out["cpu_baseline"]:

@@ -22,7 +22,8 @@ def cp(a, b):
 cp(os.path.join(src, tag + "_stats", "kernel_stats.csv"), tag + "_bench_kernel_stats.csv")
 cp(os.path.join(src, tag + "_stats", "kernel_stats_solo.csv"), tag + "_bench_kernel_stats_one_at_a_time.csv")
 cp(os.path.join(src, tag + "_stats", "bench_line.json"), tag + "_bench_line.json")
-cp(os.path.join(src, tag + "_bench_line_noprof.json"), tag + "_bench_line_noprof.json")
+cp(os.path.join(os.environ.get("BENCH_LINE_DIR", os.path.join(root, "bench_lines")), tag + "_bench_line_noprof.json"),
+   tag + "_bench_line_noprof.json")
 cp(os.path.join(src, tag + "_multimatcher_cpp.jsonl"), tag + "_multimatcher_cpp.jsonl")
 cp(os.path.join(src, tag + "_batch_scaled_testscan.txt"), tag + "_batch_scaled_testscan.txt")
 for name in ("fetch", "write", "sq", "tcc"):

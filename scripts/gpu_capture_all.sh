@@ -6,13 +6,15 @@ set -u
 TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
+LINES=${BENCH_LINE_DIR:-$ROOT/bench_lines}   # the --full bench line without a profiler (scripts/collect_profiles.py reads it there)
+mkdir -p "$LINES"
 bash scripts/gpu_profile.sh ${TAG}_stats > /dev/null 2>&1
 bash scripts/gpu_pmc.sh ${TAG}_pmc > /dev/null 2>&1
 bash scripts/gpu_pmc_detail.sh ${TAG}_detail > /dev/null 2>&1
 bash scripts/gpu_pmc_ndt.sh ${TAG}_ndt > /dev/null 2>&1
 bash scripts/gpu_pmc_other.sh ${TAG}_other > /dev/null 2>&1
 python scripts/pmc_to_json.py gpurun_out/${TAG}_pmc gpurun_out/${TAG}_pmc/pmc_latest.json gpurun_out/${TAG}_ndt gpurun_out/${TAG}_other > /dev/null
-python bench.py > gpurun_out/${TAG}_bench_line_noprof.json 2> /dev/null
+python bench.py --full > "$LINES/${TAG}_bench_line_noprof.json" 2> /dev/null
 # the C++ wave::MultiMatcher pool: at the REFERENCE'S DEFAULT queue of 10 (multi_matcher.hpp:32-34) with 1-16 workers
 # (steady state: 24 000 pairs, so that every worker's staging buffers have grown before most of the run), with a
 # deep queue, and the voxel-filtered configurations
@@ -38,3 +40,4 @@ python bench.py > gpurun_out/${TAG}_bench_line_noprof.json 2> /dev/null
   BENCH_MATCHER=ndt BENCH_QUEUE=10 BENCH_RES=5 timeout 200 ./bench_multimatcher 55000 2000 4 16 ) > gpurun_out/${TAG}_multimatcher_cpp.jsonl 2> /dev/null
 python scripts/dev/dev_batch_scaled.py 128 > gpurun_out/${TAG}_batch_scaled_testscan.txt 2> /dev/null
 ls gpurun_out/${TAG}_*
+ls "$LINES"/${TAG}_*

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bench -- \
-    python "$ROOT/bench.py" --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2>&1
+    python "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$OUT/bench_stdout.log" 2>&1
 cd "$ROOT"
 find "$OUT" -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} "$OUT/kernel_stats.csv"
 # keep the (large) per-dispatch trace out of the merge-back budget

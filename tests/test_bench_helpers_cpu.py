@@ -165,3 +165,37 @@ def test_first_sharded_step_falls_back_once_and_only_together():
         raise Boom("no")
     with pytest.raises(RuntimeError):
         bench.first_step_with_fallback(bad, lambda: None, votes, Boom)
+
+
+def test_dump_outputs_writes_the_last_steps_results(tmp_path, monkeypatch):
+    """--dump-outputs: the transform and statistics wm_icp_align returns, and the last iteration's correspondences
+    (a fixed seeded sample above DUMP_MAX_POINTS), as .npy in float64 / float32 -- the same sample on every run."""
+    import numpy as np
+    import bench
+
+    class FakeCtx:
+        def __init__(self, n):
+            self.n = n
+
+        def correspondences(self):
+            return np.arange(self.n, dtype=np.int32) - 1, np.linspace(0.0, 9.0, self.n).astype(np.float32)
+    r = {"T": np.arange(16.0).reshape(4, 4), "iterations": 50, "n_corr": 7, "mse": 0.25, "prev_mse": 0.5, "converged": True}
+    names = bench.dump_outputs(str(tmp_path / "a"), r, FakeCtx(1000))
+    assert names == ["converged", "correspondence_d2", "correspondence_index", "iterations", "mse", "n_corr", "prev_mse",
+                     "transform"]
+    load = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))  # noqa: E731
+    assert load("a", "transform").dtype == np.float64 and np.array_equal(load("a", "transform"), r["T"])
+    assert float(load("a", "mse")) == 0.25 and float(load("a", "converged")) == 1.0
+    assert load("a", "correspondence_index").dtype == np.float64 and load("a", "correspondence_index")[0] == -1.0
+    assert load("a", "correspondence_d2").dtype == np.float32 and len(load("a", "correspondence_d2")) == 1000
+    # above the cap: a sample of fixed size, identical from run to run; at the cap the dump stays within 64 MB
+    # (8-byte index + 4-byte d2 + 8-byte sample position per point)
+    assert 20 * bench.DUMP_MAX_POINTS < 64 * 2**20
+    monkeypatch.setattr(bench, "DUMP_MAX_POINTS", 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), r, FakeCtx(1000))
+    pick = load("b", "correspondence_sample")
+    assert len(pick) == 100 and np.array_equal(pick, load("c", "correspondence_sample")) and np.all(np.diff(pick) > 0)
+    assert np.array_equal(load("b", "correspondence_index"), pick - 1.0)
+    # a sharded registration (no single context): transform and statistics only
+    assert "correspondence_index" not in bench.dump_outputs(str(tmp_path / "s"), r)

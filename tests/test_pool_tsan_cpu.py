@@ -2,6 +2,7 @@
 producers, six workers and a consumer hammer the queues; any data race TSan sees fails the test.
 CPU only -- the pool is a template, exercised here with a matcher that needs no device."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -19,7 +20,10 @@ def test_multimatcher_pool_is_race_free_under_tsan(tmp_path):
     if build.returncode != 0 and ("libtsan" in build.stderr or "-ltsan" in build.stderr):
         pytest.skip("no ThreadSanitizer runtime in this toolchain")
     assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=600,
+    # (address-space randomisation off for this one process: TSan's fixed shadow layout does not cover where a kernel with
+    # more mmap randomisation bits places the executable -- "FATAL: ThreadSanitizer: unexpected memory mapping")
+    cmd = ["setarch", platform.machine(), "-R", exe] if shutil.which("setarch") else [exe]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66"))
     assert "WARNING: ThreadSanitizer" not in run.stderr, run.stderr[-3000:]
     assert run.returncode == 0 and "OK" in run.stdout, (run.returncode, run.stdout, run.stderr[-1000:])

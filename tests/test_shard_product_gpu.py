@@ -401,7 +401,7 @@ def test_bench_sharded_under_torch_distributed_run():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "200000", "--no-cpu-baseline",
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "200000", "--full", "--no-cpu-baseline",
            "--no-other-configs"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
