@@ -87,7 +87,17 @@ def lum_info(final, tgt, pairs=None, max_corr=None):
         i, j = np.flatnonzero(keep), j[keep]
     else:
         i, j = pairs
-    p, q = final[i].astype(np.float32), tgt[j].astype(np.float32)
+    MM, D, terms = lum_normal_equations(final[i], tgt[j])
+    ss = np.float32(0)
+    for t in terms:   # `float ss` += static_cast<float>(...): a sequential float sum
+        ss = np.float32(ss + t)
+    return MM * float(np.float32(1.0) / ss), int(len(i)), float(ss)
+
+
+def lum_normal_equations(p, q):
+    """lum_info's per-pair algebra on aligned pairs (p, q): M'M (6x6), D = (M'M)^-1 M'Z, and the float
+    residual terms |diff - (D_t + av x D_r)|^2 that the reference adds into its float s^2."""
+    p, q = p.astype(np.float32), q.astype(np.float32)
     av = np.float32(0.5) * (p + q)
     df = p - q
     a0, a1, a2 = (av[:, k].astype(np.float64) for k in range(3))
@@ -105,7 +115,7 @@ def lum_info(final, tgt, pairs=None, max_corr=None):
     MM[3, 3] = (av[:, 1] * av[:, 1] + av[:, 2] * av[:, 2]).astype(np.float64).sum()
     MM[4, 4] = (av[:, 0] * av[:, 0] + av[:, 1] * av[:, 1]).astype(np.float64).sum()
     MM[5, 5] = (av[:, 0] * av[:, 0] + av[:, 2] * av[:, 2]).astype(np.float64).sum()
-    MM[0, 0] = MM[1, 1] = MM[2, 2] = float(len(i))
+    MM[0, 0] = MM[1, 1] = MM[2, 2] = float(len(p))
     for r, c in ((4, 0), (5, 0), (3, 1), (4, 1), (3, 2), (5, 2), (4, 3), (5, 3), (5, 4)):
         MM[r, c] = MM[c, r]
     MZ = np.zeros(6)
@@ -119,11 +129,7 @@ def lum_info(final, tgt, pairs=None, max_corr=None):
     e0 = d[:, 0] - (D[0] + a[:, 2] * D[5] - a[:, 1] * D[4])
     e1 = d[:, 1] - (D[1] + a[:, 0] * D[4] - a[:, 2] * D[3])
     e2 = d[:, 2] - (D[2] + a[:, 1] * D[3] - a[:, 0] * D[5])
-    terms = (e0 * e0 + e1 * e1 + e2 * e2).astype(np.float32)
-    ss = np.float32(0)
-    for t in terms:   # `float ss` += static_cast<float>(...): a sequential float sum
-        ss = np.float32(ss + t)
-    return MM * float(np.float32(1.0) / ss), int(len(i)), float(ss)
+    return MM, D, (e0 * e0 + e1 * e1 + e2 * e2).astype(np.float32)
 
 
 def icp(src, tgt, max_corr=3.0, max_iter=100, t_eps=1e-8, fit_eps=1e-2, prev_mse=None):
