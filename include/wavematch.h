@@ -581,6 +581,56 @@ int wm_icp_info_sharded(wm_ctx *ctx, wm_comm *comm, int method, const double T_r
  * callback, no host bounce.  comm == NULL switches sharding off. */
 int wm_ndt_set_comm(wm_ctx *ctx, wm_comm *comm);
 
+/* --------------------------------------------------------- ground segmentation */
+/* wave::GroundSegmentationParams (wave_matching/include/wave/matching/ground_segmentation_params.hpp:10-37):
+ * the same fields, types and defaults (wm_ground_default_params). */
+typedef struct {
+    double rmax;            /* :11  points at this radius or beyond get no label */
+    int max_bin_points;     /* :12  parsed, never used (as in the reference) */
+    int num_seed_points;    /* :13  seeds per sector; < 0: every eligible signal point */
+    float p_l;              /* :16  GP length scale (> 0) */
+    float p_sf;             /* :18  GP signal scale (> 0) */
+    float p_sn;             /* :19  GP noise (> 0) */
+    float p_tmodel;         /* :20  inlier: predicted variance below this ... */
+    float p_tdata;          /* :23  ... and normalised residual below this */
+    float p_tg;             /* :25  ground: within this of the model height */
+    double robot_height;    /* :28  overhanging: above this over the model */
+    double max_seed_range;  /* :31 */
+    double max_seed_height; /* :32 */
+    int num_bins_a;         /* :34  angular sectors (> 0) */
+    int num_bins_l;         /* :35  linear bins per sector (> 0) */
+} wm_ground_params;
+void wm_ground_default_params(wm_ground_params *p);
+
+/* per-point labels (labels_out) and the lists of the keep mask */
+enum { WM_GROUND_NONE = 0, WM_GROUND_GROUND = 1, WM_GROUND_OBSTACLE = 2, WM_GROUND_OVERHANGING = 3 };
+enum { WM_KEEP_GROUND = 1, WM_KEEP_OBSTACLE = 2, WM_KEEP_OVERHANGING = 4 };
+
+typedef struct {
+    size_t n_ground, n_obstacle, n_overhanging;  /* the three lists' sizes, whatever the keep mask */
+    size_t n_in_range;                           /* points with radius < rmax */
+    int n_signal_cells;                          /* cells of more than 5 points (impl :123) */
+    int n_model_cells;                           /* cells in a sector's final ground model (seeds included) */
+    int n_sufficient_sectors;                    /* sectors with at least 2 seeds (impl :182) */
+    int passes_total, passes_max;                /* INSAC passes, summed and the largest of a sector */
+} wm_ground_stats;
+
+/* GroundSegmentation<PointT>::applyFilter (wave_matching/include/wave/matching/impl/ground_segmentation.hpp:358-381):
+ * genPolarBinGrid (:36-84) and sectorINSAC per sector (:108-355) on the device.  The indices of the kept lists --
+ * ground, then obstacle, then overhanging, each ordered by sector, within a sector model cells (model order) then
+ * the remaining cells (ascending height), within a cell ascending index -- go to indices_out (`out_mem` says where
+ * it lives, as labels_out, whose n entries are WM_GROUND_* per input point; NULL: not wanted).  *n_out = the kept
+ * points; more than `cap`: WM_ERR_ARG (the first `cap` are written).  Every call classifies its input afresh.
+ * Parameters that would make the reference index out of bounds or divide into NaN are WM_ERR_ARG: num_bins_a or
+ * num_bins_l <= 0, p_l, p_sf or p_sn <= 0, any non-finite value.  num_bins_a * num_bins_l above 2^24, or device
+ * memory short of what the sectors' GP factors need (m^2 + m (m + 1) / 2 doubles for a sector of m signal cells):
+ * WM_ERR_NOMEM.  The workspace is the context's own (grown on demand -- a call whose factors outgrow it runs its
+ * sector stage twice -- and freed by wm_ctx_destroy); a context's registration state (clouds, grid, models) is not
+ * touched. */
+int wm_ground_segment(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                      const wm_ground_params *params, int keep_mask, int32_t *indices_out, size_t cap, int out_mem,
+                      size_t *n_out, uint8_t *labels_out /* NULL ok */, wm_ground_stats *stats /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

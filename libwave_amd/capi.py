@@ -88,6 +88,23 @@ class NdtStats(C.Structure):
                 ("model_builds", C.c_int)]
 
 
+class GroundParams(C.Structure):
+    _fields_ = [("rmax", C.c_double), ("max_bin_points", C.c_int), ("num_seed_points", C.c_int),
+                ("p_l", C.c_float), ("p_sf", C.c_float), ("p_sn", C.c_float), ("p_tmodel", C.c_float),
+                ("p_tdata", C.c_float), ("p_tg", C.c_float), ("robot_height", C.c_double),
+                ("max_seed_range", C.c_double), ("max_seed_height", C.c_double), ("num_bins_a", C.c_int),
+                ("num_bins_l", C.c_int)]
+
+
+class GroundStats(C.Structure):
+    _fields_ = [("n_ground", C.c_size_t), ("n_obstacle", C.c_size_t), ("n_overhanging", C.c_size_t),
+                ("n_in_range", C.c_size_t), ("n_signal_cells", C.c_int), ("n_model_cells", C.c_int),
+                ("n_sufficient_sectors", C.c_int), ("passes_total", C.c_int), ("passes_max", C.c_int)]
+
+
+WM_GROUND_NONE, WM_GROUND_GROUND, WM_GROUND_OBSTACLE, WM_GROUND_OVERHANGING = 0, 1, 2, 3
+WM_KEEP_GROUND, WM_KEEP_OBSTACLE, WM_KEEP_OVERHANGING = 1, 2, 4
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -216,6 +233,11 @@ def lib():
         L.wm_icp_stats_for.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
         L.wm_umeyama_from_stats.argtypes = [_dp, _dp]
         L.wm_gn6_from_stats.argtypes = [_dp, _dp]
+        L.wm_ground_default_params.argtypes = [C.POINTER(GroundParams)]
+        L.wm_ground_default_params.restype = None
+        L.wm_ground_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                        C.POINTER(GroundParams), C.c_int, C.c_void_p, C.c_size_t, C.c_int,
+                                        C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(GroundStats)]
         _LIB = L
     return _LIB
 
@@ -258,6 +280,17 @@ def icp_params(**kw):
     p = IcpParams()
     lib().wm_icp_default_params(C.byref(p))
     for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def ground_params(params=None, **kw):
+    """wm_ground_params from the defaults (GroundSegmentationParams), a dict of field values and keywords."""
+    p = GroundParams()
+    lib().wm_ground_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
@@ -454,6 +487,22 @@ class Context:
             w += counts[2 * k + 1]
             res.append((a, b))
         return res
+
+    def ground_segment(self, cloud, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING):
+        """wave::GroundSegmentation's filter (wm_ground_segment) -> (labels (n,) uint8 WM_GROUND_*, indices of the
+        kept lists in output order (int32), stats dict).  `cloud`: float32 (n, 3|4) numpy array or HIP torch tensor;
+        `params`: a GroundParams, a dict of its fields, or None (the defaults)."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        p = params if isinstance(params, GroundParams) else ground_params(params)
+        labels = np.zeros(max(n, 1), np.uint8)
+        idx = np.empty(max(n, 1), np.int32)
+        m = C.c_size_t(0)
+        st = GroundStats()
+        self._check(lib().wm_ground_segment(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), int(keep),
+                                            C.c_void_p(idx.ctypes.data), n, WM_MEM_HOST, C.byref(m),
+                                            C.c_void_p(labels.ctypes.data), C.byref(st)), "wm_ground_segment")
+        stats = {k: getattr(st, k) for k, _ in GroundStats._fields_}
+        return labels[:n].copy(), idx[:m.value].copy(), stats
 
     def voxel_downsample(self, cloud, leaf):
         ptr, n, stride, mem, keep = _cloud_arg(cloud)

@@ -1128,6 +1128,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     gicp_small_release(ctx);
     ndt_small_release(ctx);
     batch_voxel_release(ctx);
+    ground_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

@@ -185,6 +185,7 @@ struct wm_ctx {
     void *gicp_small_batch = nullptr;       // wm_gicp_small.hip: ... of the batched small GICP registrations
     void *ndt_small_batch = nullptr;        // wm_ndt_small.hip: ... of the batched small NDT registrations
     void *batch_voxel = nullptr;            // wm_batch.hip: buffers of the batched voxel filter
+    void *ground = nullptr;                 // wm_ground.hip: the ground filter's workspace (its own, shared with nothing)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -481,6 +482,7 @@ int small_run(wm_ctx *ctx, const SmallJob *jobs, int n, size_t stride, int mem, 
               double info_max_corr, SmallResult *res, float *kernel_ms);
 void small_fill_stats(const SmallResult &r, float kernel_ms, wm_icp_stats *s);
 void batch_voxel_release(wm_ctx *ctx);
+void ground_release(wm_ctx *ctx);  // wm_ground.hip
 int batch_match_scaled(wm_ctx *ctx, const wm_batch_item *items, int n_items, size_t stride, int mem,
                        const wm_icp_params *p, float res, int multiscale_steps, int with_info, double *T_out,
                        double *info_out, wm_icp_stats *stats, int *status);
