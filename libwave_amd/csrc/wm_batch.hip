@@ -17,7 +17,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "wm_internal.hpp"
+#include "wm_stage.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -258,14 +258,11 @@ __global__ void __launch_bounds__(kBlock)
 
 // ------------------------------------------------------------------ host side
 struct BatchVoxel {
-    DevBuf raw;        // the uploaded clouds (host input)
+    SliceUpload raw;   // the uploaded clouds (host input)
     DevBuf table;      // VbCloud[], VbBox[], VbLeaf[], skip[], n_out[], VbXform[]
     DevBuf packed, out;
     DevBuf key, key2, perm, perm2, flags, seg, heads, tmp;
-    void *h_raw = nullptr;
-    size_t h_raw_cap = 0;
-    void *h_tab = nullptr;
-    size_t h_tab_cap = 0;
+    PinnedBuf h_tab;
 };
 
 static BatchVoxel *voxel_of(wm_ctx *ctx) {
@@ -276,26 +273,13 @@ static BatchVoxel *voxel_of(wm_ctx *ctx) {
 void batch_voxel_release(wm_ctx *ctx) {
     BatchVoxel *b = static_cast<BatchVoxel *>(ctx->batch_voxel);
     if (!b) return;
-    DevBuf *bufs[] = {&b->raw, &b->table, &b->packed, &b->out, &b->key, &b->key2, &b->perm, &b->perm2, &b->flags, &b->seg, &b->heads, &b->tmp};
+    DevBuf *bufs[] = {&b->table, &b->packed, &b->out, &b->key, &b->key2, &b->perm, &b->perm2, &b->flags, &b->seg, &b->heads, &b->tmp};
     for (DevBuf *d : bufs) d->release();
-    if (b->h_raw) (void) hipHostFree(b->h_raw);
-    if (b->h_tab) (void) hipHostFree(b->h_tab);
+    b->raw.release();
+    b->h_tab.release();
     delete b;
     ctx->batch_voxel = nullptr;
 }
-
-static int pinned_grow(wm_ctx *ctx, void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return WM_OK;
-    if (*p) (void) hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    WM_HIP(ctx, hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return WM_OK;
-}
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // The clouds of one sub-batch on the device, packed, with their bounding boxes: what every scale's
 // filter starts from.  Cloud 2 j = ref of pair j, 2 j + 1 = its target.
@@ -328,17 +312,17 @@ struct VoxelBatch {
                 cl[2 * j + s].n = (unsigned) n2[s];
                 cl[2 * j + s].off = (unsigned) total;
                 total += n2[s];
-                raw_bytes += align_up(n2[s] * stride, 16);
+                raw_bytes += align_up256(n2[s] * stride);
             }
         }
         if (total == 0 || total > 0x7FFFFFF0u) return WM_ERR_ARG;
         o_cloud = 0;
-        o_box = align_up(o_cloud + n_clouds * sizeof(VbCloud), 256);
-        o_leaf = align_up(o_box + n_clouds * sizeof(VbBox), 256);
-        o_skip = align_up(o_leaf + n_clouds * sizeof(VbLeaf), 256);
-        o_nout = align_up(o_skip + n_clouds, 256);
-        o_xf = align_up(o_nout + n_clouds * sizeof(unsigned), 256);
-        tab_bytes = align_up(o_xf + n_pairs * sizeof(VbXform), 256);
+        o_box = align_up256(o_cloud + n_clouds * sizeof(VbCloud));
+        o_leaf = align_up256(o_box + n_clouds * sizeof(VbBox));
+        o_skip = align_up256(o_leaf + n_clouds * sizeof(VbLeaf));
+        o_nout = align_up256(o_skip + n_clouds);
+        o_xf = align_up256(o_nout + n_clouds * sizeof(unsigned));
+        tab_bytes = align_up256(o_xf + n_pairs * sizeof(VbXform));
         WM_HIP(ctx, V->table.reserve(tab_bytes));
         WM_HIP(ctx, V->packed.reserve(total * sizeof(float4)));
         WM_HIP(ctx, V->out.reserve(total * sizeof(float4)));
@@ -349,37 +333,17 @@ struct VoxelBatch {
         WM_HIP(ctx, V->flags.reserve(total * 4));
         WM_HIP(ctx, V->seg.reserve((total + 1) * 4));
         WM_HIP(ctx, V->heads.reserve((total + 2) * 4));
-        WM_TRY(pinned_grow(ctx, &V->h_tab, &V->h_tab_cap, tab_bytes));
+        WM_HIP(ctx, V->h_tab.reserve(tab_bytes));
         WM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the staging buffers may still feed the previous sub-batch)
-        ht = static_cast<unsigned char *>(V->h_tab);
+        ht = V->h_tab.as<unsigned char>();
         dt = V->table.as<unsigned char>();
-        // the clouds onto the device (host input: through pinned memory, DMA of one slice under the next copy)
-        if (mem == WM_MEM_HOST) {
-            WM_HIP(ctx, V->raw.reserve(raw_bytes));
-            WM_TRY(pinned_grow(ctx, &V->h_raw, &V->h_raw_cap, raw_bytes));
-            unsigned char *h = static_cast<unsigned char *>(V->h_raw), *d = V->raw.as<unsigned char>();
-            size_t off = 0, sent = 0;
-            for (unsigned j = 0; j < n_pairs; ++j) {
-                const wm_batch_item &it = items[idx[j]];
-                const void *src2[2] = {it.src, it.target};
-                const size_t n2[2] = {it.n_src, it.n_target};
-                for (int s = 0; s < 2; ++s) {
-                    if (n2[s]) memcpy(h + off, src2[s], n2[s] * stride);
-                    cl[2 * j + s].raw = d + off;
-                    off += align_up(n2[s] * stride, 16);
-                    if (off - sent >= ((size_t) 2 << 20)) {
-                        WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-                        sent = off;
-                    }
-                }
-            }
-            if (off > sent) WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            for (unsigned j = 0; j < n_pairs; ++j) {
-                cl[2 * j].raw = static_cast<const unsigned char *>(items[idx[j]].src);
-                cl[2 * j + 1].raw = static_cast<const unsigned char *>(items[idx[j]].target);
-            }
+        // the clouds' addresses on the device (host input: through pinned memory in slices, wm_stage.hpp)
+        WM_TRY(V->raw.begin(ctx, 0, raw_bytes, mem));
+        for (unsigned c = 0; c < n_clouds; ++c) {
+            const wm_batch_item &it = items[idx[c / 2]];
+            WM_TRY(V->raw.add(ctx, c & 1 ? it.target : it.src, cl[c].n * stride, &cl[c].raw));
         }
+        WM_TRY(V->raw.flush(ctx));
         memcpy(ht + o_cloud, cl.data(), n_clouds * sizeof(VbCloud));
         h_skip = ht + o_skip;
         memset(h_skip, 0, n_clouds);

@@ -20,7 +20,7 @@
 // iteration and evaluation counts (tests/test_gicp_batch_gpu.py asserts np.array_equal).  The GUARANTEE
 // (include/wavematch.h) stays 1e-6 m / 1e-6 rad: the double sin / cos of the gradient's rotation are the device
 // library's; a last-bit difference there showed once, after 300 evaluations of a registration that does not converge.
-#include "wm_internal.hpp"
+#include "wm_stage.hpp"
 #include "wm_gicp_dev.hpp"
 #include "wm_bfgs.hpp"
 #include "wm_gicp_quad.hpp"
@@ -30,7 +30,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 namespace wm {
@@ -756,108 +755,45 @@ __global__ void __launch_bounds__(kGsThreads) k_gicp_small(const GsPair *__restr
 }
 
 // ---- host
-struct GicpSmallBatch {
-    DevBuf d_stage;  // [table | clouds]
-    DevBuf d_work;   // the pairs' scratch
-    DevBuf d_out;
-    void *h_stage = nullptr;
-    size_t h_stage_cap = 0;
-    void *h_out = nullptr;
-    size_t h_out_cap = 0;
-};
-
-static GicpSmallBatch *gs_of(wm_ctx *ctx) {
-    if (!ctx->gicp_small_batch) ctx->gicp_small_batch = new (std::nothrow) GicpSmallBatch();
-    return static_cast<GicpSmallBatch *>(ctx->gicp_small_batch);
+// a pair's scratch in HBM
+static void gs_scratch(Carver &w, GsPair &t, size_t ns, size_t nt) {
+    t.s_pts = w.take<float4>((ns + 4) * 16);
+    t.t_pts = w.take<float4>((nt + 4) * 16);
+    t.s_cs = w.take<unsigned>(((size_t) kGsCells + 8) * 4);
+    t.t_cs = w.take<unsigned>(((size_t) kGsCells + 8) * 4);
+    t.run = w.take<unsigned>(((size_t) kGsCells + 8) * 4);
+    t.c1 = w.take<double>(ns * 72);
+    t.c2 = w.take<double>(nt * 72);
+    t.evb = w.take<unsigned char>(((ns + 63) / 64) * (size_t) kGsEvBlock);
+    t.match = w.take<unsigned>(ns * 4);
 }
-
-void gicp_small_release(wm_ctx *ctx) {
-    GicpSmallBatch *b = static_cast<GicpSmallBatch *>(ctx->gicp_small_batch);
-    if (!b) return;
-    b->d_stage.release();
-    b->d_work.release();
-    b->d_out.release();
-    if (b->h_stage) (void) hipHostFree(b->h_stage);
-    if (b->h_out) (void) hipHostFree(b->h_out);
-    delete b;
-    ctx->gicp_small_batch = nullptr;
-}
-
-
-
-struct GsJob {
-    const void *src;
-    size_t n_src;
-    const void *tgt;
-    size_t n_tgt;
-};
 
 // `n` registrations (no empty cloud among them) in one launch; out[k] = what the kernel left for job k
-static int gicp_small_run(wm_ctx *ctx, const GsJob *jobs, int n, size_t stride, int mem, const wm_gicp_params *prm, GsOut *res,
+static int gicp_small_run(wm_ctx *ctx, const PairJob *jobs, int n, size_t stride, int mem, const wm_gicp_params *prm, GsOut *res,
                           float *kernel_ms) {
     if (n <= 0) return WM_OK;
-    GicpSmallBatch *B = gs_of(ctx);
-    if (!B) return WM_ERR_NOMEM;
-    size_t cloud_bytes = 0, work_bytes = 0;
-    auto work_need = [](size_t ns, size_t nt) {
-        return align_up256((ns + 4) * 16) + align_up256((nt + 4) * 16) + 3 * align_up256(((size_t) kGsCells + 8) * 4) + align_up256(ns * 72) + align_up256(nt * 72) +
-               align_up256(((ns + 63) / 64) * (size_t) kGsEvBlock) + align_up256(ns * 4);
-    };
+    PairStage &S = ctx->gicp_stage;
+    size_t cloud_bytes = 0;
+    Carver need;  // (counts only)
+    GsPair unused;
     for (int k = 0; k < n; ++k) {
         if (jobs[k].n_src == 0 || jobs[k].n_tgt == 0 || jobs[k].n_src > (size_t) WM_GICP_BATCH_MAX_POINTS ||
             jobs[k].n_tgt > (size_t) WM_GICP_BATCH_MAX_POINTS)
             return WM_ERR_ARG;
         cloud_bytes += align_up256(jobs[k].n_src * stride) + align_up256(jobs[k].n_tgt * stride);
-        work_bytes += work_need(jobs[k].n_src, jobs[k].n_tgt);
+        gs_scratch(need, unused, jobs[k].n_src, jobs[k].n_tgt);
     }
-    const size_t table_bytes = align_up256((size_t) n * sizeof(GsPair));
-    const size_t up_bytes = table_bytes + (mem == WM_MEM_HOST ? cloud_bytes : 0);
-    WM_HIP(ctx, B->d_stage.reserve(up_bytes));
-    WM_HIP(ctx, B->d_work.reserve(work_bytes));
-    WM_HIP(ctx, B->d_out.reserve((size_t) n * sizeof(GsOut)));
-    WM_TRY(pinned_reserve(ctx, &B->h_stage, &B->h_stage_cap, up_bytes));
-    WM_TRY(pinned_reserve(ctx, &B->h_out, &B->h_out_cap, (size_t) n * sizeof(GsOut)));
-    WM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the staging buffer for the previous batch)
-    unsigned char *h = static_cast<unsigned char *>(B->h_stage), *d = B->d_stage.as<unsigned char>(), *w = B->d_work.as<unsigned char>();
-    GsPair *table = reinterpret_cast<GsPair *>(h);
-    size_t off = table_bytes, sent = table_bytes;
+    const size_t out_bytes = (size_t) n * sizeof(GsOut);
+    WM_TRY(S.begin(ctx, align_up256((size_t) n * sizeof(GsPair)), cloud_bytes, need.used, out_bytes, mem));
     for (int k = 0; k < n; ++k) {
-        const GsJob &it = jobs[k];
-        GsPair &t = table[k];
+        const PairJob &it = jobs[k];
+        GsPair &t = S.table<GsPair>()[k];
         t.n_src = (unsigned) it.n_src;
         t.n_tgt = (unsigned) it.n_tgt;
-        if (mem == WM_MEM_HOST) {
-            memcpy(h + off, it.src, it.n_src * stride);
-            t.src = d + off;
-            off += align_up256(it.n_src * stride);
-            memcpy(h + off, it.tgt, it.n_tgt * stride);
-            t.tgt = d + off;
-            off += align_up256(it.n_tgt * stride);
-            if (off - sent >= ((size_t) 2 << 20)) {  // (each slice's DMA runs under the next slices' copies)
-                WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-                sent = off;
-            }
-        } else {
-            t.src = static_cast<const unsigned char *>(it.src);
-            t.tgt = static_cast<const unsigned char *>(it.tgt);
-        }
-        auto take = [&](size_t bytes) {
-            unsigned char *p = w;
-            w += align_up256(bytes);
-            return p;
-        };
-        t.s_pts = reinterpret_cast<float4 *>(take((it.n_src + 4) * 16));
-        t.t_pts = reinterpret_cast<float4 *>(take((it.n_tgt + 4) * 16));
-        t.s_cs = reinterpret_cast<unsigned *>(take(((size_t) kGsCells + 8) * 4));
-        t.t_cs = reinterpret_cast<unsigned *>(take(((size_t) kGsCells + 8) * 4));
-        t.run = reinterpret_cast<unsigned *>(take(((size_t) kGsCells + 8) * 4));
-        t.c1 = reinterpret_cast<double *>(take(it.n_src * 72));
-        t.c2 = reinterpret_cast<double *>(take(it.n_tgt * 72));
-        t.evb = take(((it.n_src + 63) / 64) * (size_t) kGsEvBlock);
-        t.match = reinterpret_cast<unsigned *>(take(it.n_src * 4));
+        WM_TRY(S.up.add(ctx, it.src, it.n_src * stride, &t.src));
+        WM_TRY(S.up.add(ctx, it.tgt, it.n_tgt * stride, &t.tgt));
+        gs_scratch(S.work, t, it.n_src, it.n_tgt);
     }
-    if (off > sent) WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(d, h, table_bytes, hipMemcpyHostToDevice, ctx->stream));
     GsParams P;
     memset(&P, 0, sizeof(P));
     P.stride = (unsigned) stride;
@@ -877,18 +813,15 @@ static int gicp_small_run(wm_ctx *ctx, const GsJob *jobs, int n, size_t stride, 
 #ifndef WM_GICP_SMALL_EXPERIMENTS
     P.debug &= 1;
 #endif
-    WM_HIP(ctx, hipEventRecord(ctx->ev_a, ctx->stream));
-    const GsPair *dt = reinterpret_cast<const GsPair *>(d);
+    WM_TRY(S.submit(ctx));
+    const GsPair *dt = S.d_table<GsPair>();
     if (P.k <= 10)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<10>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, B->d_out.as<GsOut>());
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<10>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, S.d_out.as<GsOut>());
     else if (P.k <= 20)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<20>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, B->d_out.as<GsOut>());
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<20>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, S.d_out.as<GsOut>());
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<32>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, B->d_out.as<GsOut>());
-    WM_HIP(ctx, hipGetLastError());
-    WM_HIP(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(B->h_out, B->d_out.p, (size_t) n * sizeof(GsOut), hipMemcpyDeviceToHost, ctx->stream));
-    WM_TRY(sync_sleeping(ctx));  // (milliseconds: the registrations of the whole batch)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_small<32>), dim3((unsigned) n), dim3(kGsThreads), 0, ctx->stream, dt, P, S.d_out.as<GsOut>());
+    WM_TRY(S.collect(ctx, out_bytes, kernel_ms));
 #ifdef WM_COV_COUNT
     {
         double c[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -898,8 +831,7 @@ static int gicp_small_run(wm_ctx *ctx, const GsJob *jobs, int n, size_t stride, 
                 c[0], c[1], c[1] * 64, 100.0 * c[0] / (c[1] * 64 + 1), c[2], c[3], c[4]);
     }
 #endif
-    if (kernel_ms) (void) hipEventElapsedTime(kernel_ms, ctx->ev_a, ctx->ev_b);
-    memcpy(res, B->h_out, (size_t) n * sizeof(GsOut));
+    memcpy(res, S.h_out.p, out_bytes);
     return WM_OK;
 }
 
@@ -925,7 +857,7 @@ int wm_gicp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, si
     }
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats) * (size_t) n_items);
-    std::vector<GsJob> jobs;
+    std::vector<PairJob> jobs;
     std::vector<int> item_of;
     std::vector<int> one_by_one;
     size_t run_stride = stride;
@@ -947,7 +879,7 @@ int wm_gicp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, si
             }
             status[k] = (ns == 0 || nt == 0) ? WM_ERR_STATE : WM_OK;
             if (status[k] != WM_OK) continue;
-            jobs.push_back(GsJob{filtered + off[2 * (size_t) k], ns, filtered + off[2 * (size_t) k + 1], nt});
+            jobs.push_back(PairJob{filtered + off[2 * (size_t) k], ns, filtered + off[2 * (size_t) k + 1], nt});
             item_of.push_back(k);
         }
         run_stride = sizeof(float4);
@@ -958,7 +890,7 @@ int wm_gicp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, si
             // (wm_gicp_align on an empty cloud: WM_ERR_STATE)
             status[k] = (it.n_src == 0 || it.n_target == 0) ? WM_ERR_STATE : WM_OK;
             if (status[k] != WM_OK) continue;
-            jobs.push_back(GsJob{it.src, it.n_src, it.target, it.n_target});
+            jobs.push_back(PairJob{it.src, it.n_src, it.target, it.n_target});
             item_of.push_back(k);
         }
     }

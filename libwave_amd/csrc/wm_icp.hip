@@ -1124,9 +1124,9 @@ void wm_ctx_destroy(wm_ctx *ctx) {
                       &ctx->shard_ref_band, &ctx->shard_tgt_band, &ctx->shard_misc, &ctx->shard_flags, &ctx->shard_pos_t,
                       &ctx->shard_pos_s, &ctx->shard_stats, &ctx->ndt_sum_dev, &ctx->corr_tmp_idx, &ctx->corr_tmp_d2, &ctx->d_state};
     for (DevBuf *b : bufs) b->release();
-    small_batch_release(ctx);
-    gicp_small_release(ctx);
-    ndt_small_release(ctx);
+    ctx->icp_stage.release();
+    ctx->gicp_stage.release();
+    ctx->ndt_stage.release();
     batch_voxel_release(ctx);
     ground_release(ctx);
     for (auto &l : ctx->levels) {

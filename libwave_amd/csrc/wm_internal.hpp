@@ -65,6 +65,98 @@ struct DevBuf {
     }
 };
 
+// The same for pinned host memory (hipHostMalloc): grows, never shrinks.
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const size_t want = bytes + bytes / 4 + 4096;
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void) hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T *as() const {
+        return reinterpret_cast<T *>(p);
+    }
+};
+
+inline size_t align_up256(size_t v) { return (v + 255) & ~(size_t) 255; }
+
+// ---------------------------------------------- staging of the batched paths
+// (wm_small.hip, wm_gicp_small.hip, wm_ndt_small.hip, wm_batch.hip; the functions: wm_stage.hpp)
+// Hands out 256-byte aligned pieces of a block one after the other.  Without a block it only counts:
+// a path states its pairs' scratch layout once, as calls of take(), and runs it twice.
+struct Carver {
+    unsigned char *base = nullptr;
+    size_t used = 0;
+    template <class T>
+    T *take(size_t bytes) {
+        unsigned char *p = base ? base + used : nullptr;
+        used += align_up256(bytes);
+        return reinterpret_cast<T *>(p);
+    }
+};
+
+// A batch's clouds on their way to the kernels.  Host memory: copied into a pinned mirror back to back
+// and sent in slices of 2 MB, so that each slice's DMA runs under the next copies; device memory: taken
+// where it is.  The first `head` bytes are the caller's (a table it fills meanwhile and sends last).
+struct SliceUpload {
+    DevBuf dev;
+    PinnedBuf host;
+    size_t off = 0, sent = 0;
+    bool host_clouds = false;
+    // room for the batch; the caller waits for the stream (it may still read the mirror) before the first add()
+    inline int begin(wm_ctx *ctx, size_t head, size_t cloud_bytes, int mem);
+    inline int add(wm_ctx *ctx, const void *pts, size_t bytes, const unsigned char **on_device);  // -> the address a kernel shall read
+    inline int flush(wm_ctx *ctx);  // sends what is still pending
+    void release() {
+        dev.release();
+        host.release();
+    }
+};
+
+struct PairJob {  // one registration of a batch: its clouds in the caller's layout, host or device memory
+    const void *src;
+    size_t n_src;
+    const void *tgt;
+    size_t n_tgt;
+};
+
+// One batch of registrations, a workgroup each: [table | host clouds] up, the pairs' scratch, the outputs back.
+struct PairStage {
+    SliceUpload up;
+    DevBuf d_work, d_out;
+    PinnedBuf h_out;
+    Carver work;  // of d_work
+    size_t table_bytes = 0;
+    // the buffers, the wait for the stream (it may still read the mirror of the previous batch), the cursors
+    inline int begin(wm_ctx *ctx, size_t table_bytes_, size_t cloud_bytes, size_t work_bytes, size_t out_bytes, int mem);
+    template <class T>
+    T *table() const {  // the host mirror, rows in the caller's order
+        return up.host.as<T>();
+    }
+    template <class T>
+    const T *d_table() const {
+        return up.dev.as<const T>();
+    }
+    inline int submit(wm_ctx *ctx);  // the clouds' tail, then the table, then ev_a: the caller launches next
+    inline int collect(wm_ctx *ctx, size_t out_bytes, float *kernel_ms);  // ev_b, the outputs into h_out, the wait
+    void release() {
+        up.release();
+        d_work.release();
+        d_out.release();
+        h_out.release();
+    }
+};
+
 // ------------------------------------------------------------ uniform grid
 // One level of the target index: points cell-sorted (x fastest) in HBM, so the
 // three x-adjacent cells of a query's neighbourhood are ONE contiguous run.
@@ -181,9 +273,7 @@ struct wm_ctx {
     // scratch
     wm::DevBuf staging, staging2, cell_of, counts, block_sums, bbox_buf;
     wm::DevBuf match_pt, match_pt_bak;  // float4 per (sorted) source point: its match's xyz
-    void *small_batch = nullptr;            // wm_small.hip: staging of the batched small registrations
-    void *gicp_small_batch = nullptr;       // wm_gicp_small.hip: ... of the batched small GICP registrations
-    void *ndt_small_batch = nullptr;        // wm_ndt_small.hip: ... of the batched small NDT registrations
+    wm::PairStage icp_stage, gicp_stage, ndt_stage;  // staging of the batched small registrations (wm_small.hip, wm_gicp_small.hip, wm_ndt_small.hip)
     void *batch_voxel = nullptr;            // wm_batch.hip: buffers of the batched voxel filter
     void *ground = nullptr;                 // wm_ground.hip: the ground filter's workspace (its own, shared with nothing)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
@@ -443,21 +533,6 @@ int launch_fix_keys(wm_ctx *ctx, float thr_d2);  // after certified iterations: 
 // this align was launch_nn_cert too (its per-query bounds are still in ctx->nn_bound)
 int launch_nn_cert(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, int stats_mode,
                    unsigned *rows_out, bool bounds_valid, bool use_bins = false);
-// pinned host staging of the batched paths (wm_small.hip, wm_gicp_small.hip, wm_ndt_small.hip): grows, never shrinks
-inline int pinned_reserve(wm_ctx *ctx, void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return WM_OK;
-    if (*p) (void) hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    WM_HIP(ctx, hipHostMalloc(p, want, hipHostMallocDefault));
-    *cap = want;
-    return WM_OK;
-}
-inline size_t align_up256(size_t v) { return (v + 255) & ~(size_t) 255; }
-void small_batch_release(wm_ctx *ctx);
-void gicp_small_release(wm_ctx *ctx);
-void ndt_small_release(wm_ctx *ctx);   // wm_ndt_small.hip: ... of the batched small NDT registrations  // wm_gicp_small.hip: the staging of the batched small GICP registrations
 // wm_batch.hip: pcl::VoxelGrid of all the clouds of a batch in one pass (see there)
 int batch_voxel_filter(wm_ctx *ctx, const wm_batch_item *items, const std::vector<int> &idx, size_t stride, int mem, float leaf,
                        const float4 **filtered, std::vector<unsigned> &off, std::vector<unsigned> &n_out);

@@ -14,7 +14,7 @@
 // are formed in double-double (exact, whatever the order the counting sort left its points in) instead of one after
 // the other in point order, the passes' sums are added in another order, and exp / log / sin / cos are the device
 // library's: results agree with wm_ndt_align to ~1e-9, not bit for bit (tests: 1e-6 m / 1e-6 rad).
-#include "wm_internal.hpp"
+#include "wm_stage.hpp"
 #include "wm_ndt_dev.hpp"
 #include "wm_ndt_ctl.hpp"
 #include "wm_gicp_dev.hpp"  // dd_add
@@ -24,7 +24,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <vector>
 
 namespace wm {
@@ -692,105 +691,42 @@ __global__ void __launch_bounds__(kNsThreads) k_ndt_small(const NsPair *__restri
 }
 
 // ---- host
-struct NdtSmallBatch {
-    DevBuf d_stage;  // [table | clouds]
-    DevBuf d_work;
-    DevBuf d_out;
-    void *h_stage = nullptr;
-    size_t h_stage_cap = 0;
-    void *h_out = nullptr;
-    size_t h_out_cap = 0;
-};
-
-static NdtSmallBatch *ns_of(wm_ctx *ctx) {
-    if (!ctx->ndt_small_batch) ctx->ndt_small_batch = new (std::nothrow) NdtSmallBatch();
-    return static_cast<NdtSmallBatch *>(ctx->ndt_small_batch);
+// a pair's scratch in HBM
+static void ns_scratch(Carver &w, NsPair &t, size_t ns, size_t nt) {
+    t.start = w.take<unsigned>(((size_t) kNsCells + 8) * 4);
+    t.run = w.take<unsigned>(((size_t) kNsCells + 8) * 4);
+    t.order = w.take<unsigned>((nt > ns ? nt : ns) * 4 + 16);
+    t.table = w.take<int>((size_t) kNsCells * 4);
+    t.vox = w.take<NdtVoxel>((nt / 6 + 1) * sizeof(NdtVoxel));
+    t.meanf = w.take<float4>((nt / 6 + 1) * sizeof(float4));
+    t.spts = w.take<float4>(ns * 16 + 16);
 }
 
-void ndt_small_release(wm_ctx *ctx) {
-    NdtSmallBatch *b = static_cast<NdtSmallBatch *>(ctx->ndt_small_batch);
-    if (!b) return;
-    b->d_stage.release();
-    b->d_work.release();
-    b->d_out.release();
-    if (b->h_stage) (void) hipHostFree(b->h_stage);
-    if (b->h_out) (void) hipHostFree(b->h_out);
-    delete b;
-    ctx->ndt_small_batch = nullptr;
-}
-
-
-
-struct NsJob {
-    const void *src;
-    size_t n_src;
-    const void *tgt;
-    size_t n_tgt;
-};
-
-static int ndt_small_run(wm_ctx *ctx, const NsJob *jobs, int n, size_t stride, int mem, const wm_ndt_params *prm, NsOut *res,
+static int ndt_small_run(wm_ctx *ctx, const PairJob *jobs, int n, size_t stride, int mem, const wm_ndt_params *prm, NsOut *res,
                          float *kernel_ms) {
     if (n <= 0) return WM_OK;
-    NdtSmallBatch *B = ns_of(ctx);
-    if (!B) return WM_ERR_NOMEM;
-    size_t cloud_bytes = 0, work_bytes = 0;
-    auto work_need = [](size_t ns, size_t nt) {
-        return 2 * align_up256(((size_t) kNsCells + 8) * 4) + align_up256((nt > ns ? nt : ns) * 4 + 16) + align_up256((size_t) kNsCells * 4) +
-               align_up256((nt / 6 + 1) * sizeof(NdtVoxel)) + align_up256((nt / 6 + 1) * sizeof(float4)) + align_up256(ns * 16 + 16);
-    };
+    PairStage &S = ctx->ndt_stage;
+    size_t cloud_bytes = 0;
+    Carver need;  // (counts only)
+    NsPair unused;
     for (int k = 0; k < n; ++k) {
         if (jobs[k].n_src == 0 || jobs[k].n_tgt == 0 || jobs[k].n_src > (size_t) WM_NDT_BATCH_MAX_POINTS ||
             jobs[k].n_tgt > (size_t) WM_NDT_BATCH_MAX_POINTS)
             return WM_ERR_ARG;
         cloud_bytes += align_up256(jobs[k].n_src * stride) + align_up256(jobs[k].n_tgt * stride);
-        work_bytes += work_need(jobs[k].n_src, jobs[k].n_tgt);
+        ns_scratch(need, unused, jobs[k].n_src, jobs[k].n_tgt);
     }
-    const size_t table_bytes = align_up256((size_t) n * sizeof(NsPair));
-    const size_t up_bytes = table_bytes + (mem == WM_MEM_HOST ? cloud_bytes : 0);
-    WM_HIP(ctx, B->d_stage.reserve(up_bytes));
-    WM_HIP(ctx, B->d_work.reserve(work_bytes));
-    WM_HIP(ctx, B->d_out.reserve((size_t) n * sizeof(NsOut)));
-    WM_TRY(pinned_reserve(ctx, &B->h_stage, &B->h_stage_cap, up_bytes));
-    WM_TRY(pinned_reserve(ctx, &B->h_out, &B->h_out_cap, (size_t) n * sizeof(NsOut)));
-    WM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the staging buffer for the previous batch)
-    unsigned char *h = static_cast<unsigned char *>(B->h_stage), *d = B->d_stage.as<unsigned char>(), *w = B->d_work.as<unsigned char>();
-    NsPair *table = reinterpret_cast<NsPair *>(h);
-    size_t off = table_bytes, sent = table_bytes;
+    const size_t out_bytes = (size_t) n * sizeof(NsOut);
+    WM_TRY(S.begin(ctx, align_up256((size_t) n * sizeof(NsPair)), cloud_bytes, need.used, out_bytes, mem));
     for (int k = 0; k < n; ++k) {
-        const NsJob &it = jobs[k];
-        NsPair &t = table[k];
+        const PairJob &it = jobs[k];
+        NsPair &t = S.table<NsPair>()[k];
         t.n_src = (unsigned) it.n_src;
         t.n_tgt = (unsigned) it.n_tgt;
-        if (mem == WM_MEM_HOST) {
-            memcpy(h + off, it.src, it.n_src * stride);
-            t.src = d + off;
-            off += align_up256(it.n_src * stride);
-            memcpy(h + off, it.tgt, it.n_tgt * stride);
-            t.tgt = d + off;
-            off += align_up256(it.n_tgt * stride);
-            if (off - sent >= ((size_t) 2 << 20)) {
-                WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-                sent = off;
-            }
-        } else {
-            t.src = static_cast<const unsigned char *>(it.src);
-            t.tgt = static_cast<const unsigned char *>(it.tgt);
-        }
-        auto take = [&](size_t bytes) {
-            unsigned char *p = w;
-            w += align_up256(bytes);
-            return p;
-        };
-        t.start = reinterpret_cast<unsigned *>(take(((size_t) kNsCells + 8) * 4));
-        t.run = reinterpret_cast<unsigned *>(take(((size_t) kNsCells + 8) * 4));
-        t.order = reinterpret_cast<unsigned *>(take((it.n_tgt > it.n_src ? it.n_tgt : it.n_src) * 4 + 16));
-        t.table = reinterpret_cast<int *>(take((size_t) kNsCells * 4));
-        t.vox = reinterpret_cast<NdtVoxel *>(take((it.n_tgt / 6 + 1) * sizeof(NdtVoxel)));
-        t.meanf = reinterpret_cast<float4 *>(take((it.n_tgt / 6 + 1) * sizeof(float4)));
-        t.spts = reinterpret_cast<float4 *>(take(it.n_src * 16 + 16));
+        WM_TRY(S.up.add(ctx, it.src, it.n_src * stride, &t.src));
+        WM_TRY(S.up.add(ctx, it.tgt, it.n_tgt * stride, &t.tgt));
+        ns_scratch(S.work, t, it.n_src, it.n_tgt);
     }
-    if (off > sent) WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(d, h, table_bytes, hipMemcpyHostToDevice, ctx->stream));
     NsParams P;
     memset(&P, 0, sizeof(P));
     P.stride = (unsigned) stride;
@@ -803,15 +739,11 @@ static int ndt_small_run(wm_ctx *ctx, const NsJob *jobs, int n, size_t stride, i
     P.skip_line_search = prm->skip_line_search;
     P.pcl_d1_sign = prm->pcl_d1_sign;
     P.spec_hessian = ctx->tune_ndt_spec_hessian;
-    WM_HIP(ctx, hipEventRecord(ctx->ev_a, ctx->stream));
-    hipLaunchKernelGGL(k_ndt_small, dim3((unsigned) n), dim3(kNsThreads), 0, ctx->stream, reinterpret_cast<const NsPair *>(d), P,
-                       threshold_d2_strict(prm->res), B->d_out.as<NsOut>());
-    WM_HIP(ctx, hipGetLastError());
-    WM_HIP(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(B->h_out, B->d_out.p, (size_t) n * sizeof(NsOut), hipMemcpyDeviceToHost, ctx->stream));
-    WM_TRY(sync_sleeping(ctx));
-    if (kernel_ms) (void) hipEventElapsedTime(kernel_ms, ctx->ev_a, ctx->ev_b);
-    memcpy(res, B->h_out, (size_t) n * sizeof(NsOut));
+    WM_TRY(S.submit(ctx));
+    hipLaunchKernelGGL(k_ndt_small, dim3((unsigned) n), dim3(kNsThreads), 0, ctx->stream, S.d_table<NsPair>(), P,
+                       threshold_d2_strict(prm->res), S.d_out.as<NsOut>());
+    WM_TRY(S.collect(ctx, out_bytes, kernel_ms));
+    memcpy(res, S.h_out.p, out_bytes);
     return WM_OK;
 }
 
@@ -835,13 +767,13 @@ int wm_ndt_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
     }
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats) * (size_t) n_items);
-    std::vector<NsJob> jobs;
+    std::vector<PairJob> jobs;
     std::vector<int> item_of, one_by_one;
     for (int k = 0; k < n_items; ++k) {
         const wm_batch_item &it = items[k];
         status[k] = (it.n_src == 0 || it.n_target == 0) ? WM_ERR_STATE : WM_OK;  // (wm_ndt_align on an empty cloud)
         if (status[k] != WM_OK) continue;
-        jobs.push_back(NsJob{it.src, it.n_src, it.target, it.n_target});
+        jobs.push_back(PairJob{it.src, it.n_src, it.target, it.n_target});
         item_of.push_back(k);
     }
     if (!jobs.empty()) {

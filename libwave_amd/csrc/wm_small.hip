@@ -34,7 +34,7 @@
 // is for queues of pairs.  The voxel-filtered branches of match() are built on top of it in
 // wm_batch.hip (small_run below is what they call, scale by scale).
 #include "wm_icp_step.hpp"
-#include "wm_internal.hpp"
+#include "wm_stage.hpp"
 #include "wm_wave.hpp"
 
 #include <float.h>
@@ -42,7 +42,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
 #include <type_traits>
 #include <vector>
 
@@ -857,138 +856,57 @@ __global__ void __launch_bounds__(kSmThreads)
 }
 
 // ------------------------------------------------------------------ host side
-struct SmallBatch {
-    DevBuf d_stage;     // [table | clouds | seeds]
-    DevBuf d_out;
-    DevBuf d_big;       // HBM-resident targets: cell-sorted copies, cell starts, ranks
-    void *h_stage = nullptr;  // pinned mirror of table + clouds
-    size_t h_stage_cap = 0;
-    void *h_out = nullptr;
-    size_t h_out_cap = 0;
-};
-
-static SmallBatch *small_of(wm_ctx *ctx) {
-    if (!ctx->small_batch) ctx->small_batch = new (std::nothrow) SmallBatch();
-    return static_cast<SmallBatch *>(ctx->small_batch);
+// a pair's scratch in HBM
+static void sm_scratch(Carver &w, SmallPair &t, size_t ns, size_t nt) {
+    t.seed = w.take<unsigned short>(((ns + 7) & ~(size_t) 7) * sizeof(unsigned short));
+    t.sorted = w.take<float4>(ns * sizeof(float4));
+    t.csum = w.take<double>(((ns + 63) / 64) * kAcc * sizeof(double));
+    t.txyz = nullptr, t.tidx = nullptr, t.tcs = nullptr, t.trank = nullptr;
+    if (nt > (size_t) kSmMaxTgt) {  // an HBM-resident target
+        t.txyz = w.take<float>((nt + 4) * 12);
+        t.tidx = w.take<unsigned short>((nt + 4) * 2);
+        t.tcs = w.take<unsigned>(((size_t) kSmCellsHbm + 8) * 4);
+        t.trank = w.take<unsigned>(nt * 4);
+    }
 }
-
-void small_batch_release(wm_ctx *ctx) {
-    SmallBatch *b = static_cast<SmallBatch *>(ctx->small_batch);
-    if (!b) return;
-    b->d_stage.release();
-    b->d_out.release();
-    b->d_big.release();
-    if (b->h_stage) (void) hipHostFree(b->h_stage);
-    if (b->h_out) (void) hipHostFree(b->h_out);
-    delete b;
-    ctx->small_batch = nullptr;
-}
-
-
-}  // namespace wm
-
-namespace wm {
 
 // The resident registrations of `n` jobs (none empty) in one or two launches: LDS-resident targets,
-// then HBM-resident ones.  Clouds in caller memory (host: staged through pinned memory in 2 MB slices,
-// each slice's DMA under the next copy; device: read in place).  res[k] = what the kernel left.
+// then HBM-resident ones.  Clouds in caller memory (host: staged, device: read in place; wm_stage.hpp).
+// res[k] = what the kernel left.
 int small_run(wm_ctx *ctx, const SmallJob *jobs, int n, size_t stride, int mem, const wm_icp_params *p, int with_info,
               double info_max_corr, SmallResult *res, float *kernel_ms) {
     if (n <= 0) return WM_OK;
-    size_t cloud_bytes = 0, seeds = 0, sorted_pts = 0, chunk_rows = 0, big_bytes = 0;
-    int n_lds = 0, n_hbm = 0;
-    auto big_need = [](size_t n_target) {  // scratch of one HBM-resident target, 16-byte aligned pieces
-        const size_t a = ((n_target + 4) * 12 + 15) & ~(size_t) 15, b = ((n_target + 4) * 2 + 15) & ~(size_t) 15;
-        const size_t c = ((size_t) kSmCellsHbm + 8) * 4, e = (n_target * 4 + 15) & ~(size_t) 15;
-        return a + b + c + e;
-    };
+    PairStage &S = ctx->icp_stage;
+    size_t cloud_bytes = 0;
+    int n_lds = 0;
+    Carver need;  // (counts only)
+    SmallPair unused;
     for (int k = 0; k < n; ++k) {
         const SmallJob &it = jobs[k];
         if (it.n_src == 0 || it.n_tgt == 0 || it.n_tgt > (size_t) kSmMaxTgtHbm || it.n_src > 0x7FFFFFF0u) return WM_ERR_ARG;
-        cloud_bytes += ((it.n_src * stride + 15) & ~(size_t) 15) + ((it.n_tgt * stride + 15) & ~(size_t) 15);
-        seeds += (it.n_src + 7) & ~(size_t) 7;
-        sorted_pts += it.n_src;
-        chunk_rows += (it.n_src + 63) / 64;
-        if (it.n_tgt > (size_t) kSmMaxTgt) {
-            big_bytes += big_need(it.n_tgt);
-            ++n_hbm;
-        } else {
-            ++n_lds;
-        }
+        cloud_bytes += align_up256(it.n_src * stride) + align_up256(it.n_tgt * stride);
+        sm_scratch(need, unused, it.n_src, it.n_tgt);
+        n_lds += it.n_tgt <= (size_t) kSmMaxTgt;
     }
-    SmallBatch *B = small_of(ctx);
-    if (!B) return WM_ERR_NOMEM;
-    const size_t table_bytes = ((size_t) n * sizeof(SmallPair) + 255) & ~(size_t) 255;
-    const size_t up_bytes = table_bytes + (mem == WM_MEM_HOST ? cloud_bytes : 0);
-    const size_t seed_bytes = (seeds * sizeof(unsigned short) + 15) & ~(size_t) 15;
-    const size_t dev_bytes = table_bytes + (mem == WM_MEM_HOST ? cloud_bytes : 0) + seed_bytes + sorted_pts * sizeof(float4) +
-                             chunk_rows * kAcc * sizeof(double);
-    WM_HIP(ctx, B->d_stage.reserve(dev_bytes));
-    WM_HIP(ctx, B->d_out.reserve((size_t) n * sizeof(SmallOut)));
-    if (big_bytes) WM_HIP(ctx, B->d_big.reserve(big_bytes));
-    WM_TRY(pinned_reserve(ctx, &B->h_stage, &B->h_stage_cap, up_bytes));
-    WM_TRY(pinned_reserve(ctx, &B->h_out, &B->h_out_cap, (size_t) n * sizeof(SmallOut)));
-    // the stream may still be reading the staging buffer for the previous batch
-    WM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-
-    unsigned char *h = static_cast<unsigned char *>(B->h_stage);
-    unsigned char *d = B->d_stage.as<unsigned char>();
-    SmallPair *table = reinterpret_cast<SmallPair *>(h);
-    size_t off = table_bytes;
-    unsigned short *seed_base = reinterpret_cast<unsigned short *>(d + table_bytes + (mem == WM_MEM_HOST ? cloud_bytes : 0));
-    float4 *sorted_base = reinterpret_cast<float4 *>(reinterpret_cast<unsigned char *>(seed_base) + seed_bytes);
-    double *csum_base = reinterpret_cast<double *>(sorted_base + sorted_pts);
-    size_t seed_off = 0, sorted_off = 0, csum_off = 0, big_off = 0;
+    const int n_hbm = n - n_lds;
+    const size_t out_bytes = (size_t) n * sizeof(SmallOut);
+    WM_TRY(S.begin(ctx, align_up256((size_t) n * sizeof(SmallPair)), cloud_bytes, need.used, out_bytes, mem));
     // rows of the table: the LDS-resident jobs first, then the HBM-resident ones (a launch each)
     std::vector<int> row_of((size_t) n, -1);
     int next_lds = 0, next_hbm = n_lds;
-    size_t sent = table_bytes;
     for (int k = 0; k < n; ++k) {
         const SmallJob &it = jobs[k];
-        const bool big = it.n_tgt > (size_t) kSmMaxTgt;
-        row_of[(size_t) k] = big ? next_hbm++ : next_lds++;
-        SmallPair &t = table[row_of[(size_t) k]];
+        row_of[(size_t) k] = it.n_tgt > (size_t) kSmMaxTgt ? next_hbm++ : next_lds++;
+        SmallPair &t = S.table<SmallPair>()[row_of[(size_t) k]];
         t.n_src = (unsigned) it.n_src;
         t.n_tgt = (unsigned) it.n_tgt;
         t.prev_mse0 = it.prev_mse0;
         t.presorted = it.presorted ? 1u : 0u;
         t.pad0 = 0;
-        if (mem == WM_MEM_HOST) {
-            memcpy(h + off, it.src, it.n_src * stride);
-            t.src = d + off;
-            off += (it.n_src * stride + 15) & ~(size_t) 15;
-            memcpy(h + off, it.tgt, it.n_tgt * stride);
-            t.tgt = d + off;
-            off += (it.n_tgt * stride + 15) & ~(size_t) 15;
-            if (off - sent >= ((size_t) 2 << 20)) {
-                WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-                sent = off;
-            }
-        } else {
-            t.src = static_cast<const unsigned char *>(it.src);
-            t.tgt = static_cast<const unsigned char *>(it.tgt);
-        }
-        t.seed = seed_base + seed_off;
-        seed_off += (it.n_src + 7) & ~(size_t) 7;
-        t.sorted = sorted_base + sorted_off;
-        sorted_off += it.n_src;
-        t.csum = csum_base + csum_off;
-        csum_off += ((it.n_src + 63) / 64) * kAcc;
-        t.txyz = nullptr, t.tidx = nullptr, t.tcs = nullptr, t.trank = nullptr;
-        if (big) {
-            unsigned char *b = B->d_big.as<unsigned char>() + big_off;
-            t.txyz = reinterpret_cast<float *>(b);
-            b += ((it.n_tgt + 4) * 12 + 15) & ~(size_t) 15;
-            t.tidx = reinterpret_cast<unsigned short *>(b);
-            b += ((it.n_tgt + 4) * 2 + 15) & ~(size_t) 15;
-            t.tcs = reinterpret_cast<unsigned *>(b);
-            b += ((size_t) kSmCellsHbm + 8) * 4;
-            t.trank = reinterpret_cast<unsigned *>(b);
-            big_off += big_need(it.n_tgt);
-        }
+        WM_TRY(S.up.add(ctx, it.src, it.n_src * stride, &t.src));
+        WM_TRY(S.up.add(ctx, it.tgt, it.n_tgt * stride, &t.tgt));
+        sm_scratch(S.work, t, it.n_src, it.n_tgt);
     }
-    if (off > sent) WM_HIP(ctx, hipMemcpyAsync(d + sent, h + sent, off - sent, hipMemcpyHostToDevice, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(d, h, table_bytes, hipMemcpyHostToDevice, ctx->stream));
 
     double I[16];
     mat4_identity(I);
@@ -1014,21 +932,15 @@ int small_run(wm_ctx *ctx, const SmallJob *jobs, int n, size_t stride, int mem, 
     P.r0_cells = 0.5f;
     P.with_info = with_info;
     P.iter_cap = st0.max_iter + 1;
-    WM_HIP(ctx, hipEventRecord(ctx->ev_a, ctx->stream));
+    WM_TRY(S.submit(ctx));
     if (n_lds)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_icp_small<true>), dim3((unsigned) n_lds), dim3(kSmThreads), 0, ctx->stream,
-                           reinterpret_cast<const SmallPair *>(d), P, st0, B->d_out.as<SmallOut>());
+                           S.d_table<SmallPair>(), P, st0, S.d_out.as<SmallOut>());
     if (n_hbm)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_icp_small<false>), dim3((unsigned) n_hbm), dim3(kSmThreads), 0, ctx->stream,
-                           reinterpret_cast<const SmallPair *>(d) + n_lds, P, st0, B->d_out.as<SmallOut>() + n_lds);
-    WM_HIP(ctx, hipGetLastError());
-    WM_HIP(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
-    WM_HIP(ctx, hipMemcpyAsync(B->h_out, B->d_out.p, (size_t) n * sizeof(SmallOut), hipMemcpyDeviceToHost, ctx->stream));
-    WM_TRY(sync_sleeping(ctx));  // (milliseconds: the registrations of the whole batch)
-    float ms = 0;
-    (void) hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b);
-    if (kernel_ms) *kernel_ms = ms;
-    const SmallOut *o = static_cast<const SmallOut *>(B->h_out);
+                           S.d_table<SmallPair>() + n_lds, P, st0, S.d_out.as<SmallOut>() + n_lds);
+    WM_TRY(S.collect(ctx, out_bytes, kernel_ms));
+    const SmallOut *o = S.h_out.as<SmallOut>();
     for (int k = 0; k < n; ++k) {
         const SmallOut &r = o[row_of[(size_t) k]];
         SmallResult &q = res[k];

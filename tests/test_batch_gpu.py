@@ -317,3 +317,22 @@ def test_batch_fallback_pair_carries_the_mse_across_its_scales(wm, ctx):
     assert (got[1]["iterations"], got[1]["state"]) == (one["iterations"], one["state"])
     dt, ang = pose_error(got[1]["T"], one["T"])
     assert dt <= 1e-9 and ang <= 1e-10
+
+
+def test_staging_grows_and_is_reused_on_one_context(wm, ctx):
+    """One context, host clouds: a batch of 2 pairs, then 40 pairs of 8 500 to 9 900 points (8.8 MB of clouds: four 2 MB
+    slices and a tail, and every staging buffer of the context has to be reallocated), then the first batch again.  Every
+    item: the bits that the same pair gives from device-resident tensors on a fresh context."""
+    pairs = [(r, t) for r, t, _ in (synth.pair(10000 - 37 * k, seed=4000 + k, mode="resample") for k in range(42))]
+    kw = dict(with_info=True, max_corr=3.0, force_iterations=5)
+    fresh = wm.Context(0)
+    dev = [(torch.from_numpy(r).cuda(), torch.from_numpy(t).cuda()) for r, t in pairs]
+    want_small = fresh.icp_batch_match(dev[:2], **kw)
+    want_big = fresh.icp_batch_match(dev[2:], **kw)
+    fresh.close()
+    for batch, want in ((pairs[:2], want_small), (pairs[2:], want_big), (pairs[:2], want_small)):
+        got = ctx.icp_batch_match(batch, **kw)
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert g["rc"] == w["rc"] == 0 and g["iterations"] == w["iterations"] == 5
+            assert np.array_equal(g["T"], w["T"]) and np.array_equal(g["info"], w["info"])

@@ -133,3 +133,22 @@ def test_batch_follows_the_parameters(wm, ctx, kw):
         _close(g, _one(ctx, r, t, res=1.5, **kw))
     if "force_iterations" in kw:
         assert all(g["iterations"] == 6 for g in got)
+
+
+def test_staging_grows_and_is_reused_on_one_context(wm, ctx):
+    """One context, host clouds: a batch of 2 pairs, then 40 pairs of 8 500 to 9 900 points (8.8 MB of clouds: four 2 MB
+    slices and a tail, and every staging buffer of the context has to be reallocated), then the first batch again.  Every
+    item: the bits that the same pair gives from device-resident tensors on a fresh context."""
+    pairs = [(r, t) for r, t, _ in (synth.pair(10000 - 37 * k, seed=4000 + k, mode="resample") for k in range(42))]
+    assert max(len(c) for p in pairs for c in p) <= wm.WM_NDT_BATCH_MAX_POINTS
+    fresh = wm.Context(0)
+    dev = [(torch.from_numpy(r).cuda(), torch.from_numpy(t).cuda()) for r, t in pairs]
+    want_small = fresh.ndt_batch_match(dev[:2], res=2.0, force_iterations=3)
+    want_big = fresh.ndt_batch_match(dev[2:], res=2.0, force_iterations=3)
+    fresh.close()
+    for batch, want in ((pairs[:2], want_small), (pairs[2:], want_big), (pairs[:2], want_small)):
+        got = ctx.ndt_batch_match(batch, res=2.0, force_iterations=3)
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert g["rc"] == w["rc"] == 0 and g["iterations"] == w["iterations"] == 3
+            assert np.array_equal(g["T"], w["T"])
