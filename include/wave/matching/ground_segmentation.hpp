@@ -14,6 +14,9 @@
 // is created by the first filter(), so construction needs no device; bad parameters give a LOG_ERROR and an empty
 // output.  libwave_matching.so holds the pcl::PointXYZ instantiation; any other point type whose first three
 // floats are x, y, z works after #include <wave/matching/impl/ground_segmentation.hpp>.
+//
+// Addition (the reference has no such member, it filters one scan per call): filterBatch() classifies a queue of
+// scans in ONE device call (wm_ground_segment_batch) and gives per scan what setInputCloud + filter would.
 #ifndef WAVE_GROUNDSEGMENTATION_HPP
 #define WAVE_GROUNDSEGMENTATION_HPP
 
@@ -45,12 +48,18 @@ void groundRelease(wm_ctx *&ctx);
 bool groundSegmentIndices(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride,
                           const GroundSegmentationParams &params, bool keep_ground, bool keep_obs, bool keep_drv,
                           std::vector<int> &out);
+// the same for `count` scans in one device call (wm_ground_segment_batch): out[k] = scan k's kept indices
+void groundLogNullScan(size_t k);  // LOG_ERROR: entry k of a batch is null
+bool groundSegmentIndicesBatch(wm_ctx *&ctx, int device, const void *const *pts, const size_t *n, size_t count,
+                               size_t stride, const GroundSegmentationParams &params, bool keep_ground, bool keep_obs,
+                               bool keep_drv, std::vector<std::vector<int>> &out);
 }  // namespace detail
 
 template <typename PointT>
 class GroundSegmentation : public pcl::Filter<PointT> {
  public:
     using PointCloud = typename pcl::Filter<PointT>::PointCloud;
+    using PointCloudConstPtr = typename pcl::Filter<PointT>::PointCloudConstPtr;
 
     // which of the three classes filter() returns, in this order: ground, obstacle, overhanging
     // (defaults: false, true, true)
@@ -65,6 +74,12 @@ class GroundSegmentation : public pcl::Filter<PointT> {
 
     // classifies input_ on the device (wm_ground_segment) and copies the kept points to `output`
     void applyFilter(PointCloud &output) override;
+
+    // Not in the reference.  outputs[k] = what setInputCloud(inputs[k]); filter(outputs[k]); gives -- the same points
+    // in the same order with all of PointT's fields, the same width / height / is_dense -- for the whole queue in one
+    // device call.  The keep flags apply to every scan; a null entry gives an empty cloud and a LOG_ERROR; the
+    // filter's own input cloud is left alone.
+    void filterBatch(const std::vector<PointCloudConstPtr> &inputs, std::vector<PointCloud> &outputs);
 
  private:
     GroundSegmentationParams params;

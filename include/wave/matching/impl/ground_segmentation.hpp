@@ -53,6 +53,32 @@ void GroundSegmentation<PointT>::applyFilter(PointCloud &output) {
     pcl::copyPointCloud(in, out_indices, output);
 }
 
+template <typename PointT>
+void GroundSegmentation<PointT>::filterBatch(const std::vector<PointCloudConstPtr> &inputs,
+                                             std::vector<PointCloud> &outputs) {
+    static_assert(sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) % 4 == 0,
+                  "GroundSegmentation: a point type whose first three floats are x, y, z");
+    const PointCloud none;
+    std::vector<const void *> pts(inputs.size(), nullptr);
+    std::vector<size_t> n(inputs.size(), 0);
+    for (size_t k = 0; k < inputs.size(); ++k) {
+        if (!inputs[k]) {
+            detail::groundLogNullScan(k);
+            continue;
+        }
+        n[k] = inputs[k]->points.size();
+        if (n[k]) pts[k] = inputs[k]->points.data();
+    }
+    std::vector<std::vector<int>> kept;
+    if (!detail::groundSegmentIndicesBatch(this->ctx, this->device, pts.data(), n.data(), inputs.size(),
+                                           sizeof(PointT), this->params, this->keep_ground, this->keep_obs,
+                                           this->keep_drv, kept))
+        kept.assign(inputs.size(), std::vector<int>());
+    std::vector<PointCloud> result(inputs.size());  // (formed aside: `outputs` may hold the inputs' clouds)
+    for (size_t k = 0; k < inputs.size(); ++k) pcl::copyPointCloud(inputs[k] ? *inputs[k] : none, kept[k], result[k]);
+    outputs.swap(result);
+}
+
 }  // namespace wave
 
 // the reference's impl header also defines this macro: PCL_INSTANTIATE_GroundSegmentation(MyPoint) in one source file

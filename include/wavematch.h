@@ -631,6 +631,38 @@ int wm_ground_segment(wm_ctx *ctx, const void *pts, size_t n, size_t stride_byte
                       const wm_ground_params *params, int keep_mask, int32_t *indices_out, size_t cap, int out_mem,
                       size_t *n_out, uint8_t *labels_out /* NULL ok */, wm_ground_stats *stats /* NULL ok */);
 
+/* One scan of a batch: n records of `stride_bytes`, x y z first, in the memory the call's `mem` names. */
+typedef struct {
+    const void *pts;
+    size_t n;
+} wm_ground_scan;
+/* What one batch may hold.  A point's sort key is scan * (cells + 1) + cell (cells = num_bins_a * num_bins_l, the
+ * extra key per scan: out of range) in 32 bits, and a point's place in the batch a 31-bit index (as wm_ground_segment's
+ * n).  Nothing else bounds the number of scans but the device memory their cells take (WM_ERR_NOMEM / WM_ERR_HIP). */
+#define WM_GROUND_BATCH_MAX_KEYS 0xFFFFFFFFull  /* n_scans * (cells + 1) at most */
+#define WM_GROUND_BATCH_MAX_POINTS 0x7FFFFFF0ull /* the scans' points in all, at most */
+
+/* GroundSegmentation<PointT>::applyFilter (wave_matching/include/wave/matching/impl/ground_segmentation.hpp:358-381,
+ * which the reference calls once per scan) for `n_scans` scans in ONE sequence of launches and one wait for the
+ * results (a second when the factor workspace has to grow): every scan's slice of indices_out (indices local to the
+ * scan), its slice of labels_out (the scans' n entries one after the other) and stats[k] are EQUAL to what
+ * wm_ground_segment gives for that scan alone with the same `params` and `keep_mask` -- one of each per batch.
+ * offsets_out (host, n_scans + 1 entries): scan k's kept points are [offsets_out[k], offsets_out[k + 1]) of
+ * indices_out and of points_out.  points_out (NULL: not wanted): per kept index the input point's x, y, z bit for bit
+ * in records of `out_stride` bytes (>= 12, a multiple of 4; bytes beyond 12 are zero) -- in device memory a cloud
+ * wm_icp_batch_match(mem = WM_MEM_DEVICE) takes as it is.  `out_mem` says where indices_out, points_out and
+ * labels_out live.  Empty scans and scans without a finite point are legal and give empty slices; n_scans == 0 is
+ * WM_OK with offsets_out[0] = 0.  More kept points than `cap`: WM_ERR_ARG with the offsets valid (the first `cap`
+ * indices and points are written).  Argument errors (a null context, table or offsets, a bad stride, mem or keep
+ * mask, parameters wm_ground_segment refuses, a batch beyond the two limits above) are found before a device is
+ * touched.  kernel_ms (NULL ok): device time between the upload and the fetch of the counts.  The workspace is the
+ * one wm_ground_segment uses; the context's registration state is not touched. */
+int wm_ground_segment_batch(wm_ctx *ctx, const wm_ground_scan *scans, int n_scans, size_t stride_bytes, int mem,
+                            const wm_ground_params *params, int keep_mask, int32_t *indices_out, size_t cap,
+                            void *points_out /* NULL ok */, size_t out_stride, int out_mem, size_t *offsets_out,
+                            uint8_t *labels_out /* NULL ok */, wm_ground_stats *stats /* NULL ok */,
+                            float *kernel_ms /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -19,6 +19,8 @@ WM_NDT_BATCH_MAX_POINTS = 200000  # wm_ndt_batch_match: a cloud of a batched NDT
 WM_GICP_BATCH_MAX_POINTS = 100000  # wm_gicp_batch_match: a cloud of a batched GICP registration at most (after the voxel filter)
 WM_BATCH_LDS_TARGET_POINTS = 10000  # wm_icp_batch_match: targets up to this size live in one CU's LDS,
 WM_BATCH_MAX_TARGET_POINTS = 65535  # larger ones (up to this) in HBM scratch
+WM_GROUND_BATCH_MAX_KEYS = 0xFFFFFFFF  # n_scans * (num_bins_a * num_bins_l + 1) of a ground_segment_batch
+WM_GROUND_BATCH_MAX_POINTS = 0x7FFFFFF0  # its scans' points in all
 WM_MEM_HOST, WM_MEM_DEVICE = 0, 1
 WM_ICP_SVD, WM_ICP_GN6 = 0, 1
 WM_NN_AUTO, WM_NN_GRID, WM_NN_BRUTE = 0, 1, 2
@@ -94,6 +96,10 @@ class GroundParams(C.Structure):
                 ("p_tdata", C.c_float), ("p_tg", C.c_float), ("robot_height", C.c_double),
                 ("max_seed_range", C.c_double), ("max_seed_height", C.c_double), ("num_bins_a", C.c_int),
                 ("num_bins_l", C.c_int)]
+
+
+class GroundScan(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_size_t)]
 
 
 class GroundStats(C.Structure):
@@ -238,6 +244,10 @@ def lib():
         L.wm_ground_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                         C.POINTER(GroundParams), C.c_int, C.c_void_p, C.c_size_t, C.c_int,
                                         C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(GroundStats)]
+        L.wm_ground_segment_batch.argtypes = [C.c_void_p, C.POINTER(GroundScan), C.c_int, C.c_size_t, C.c_int,
+                                              C.POINTER(GroundParams), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p,
+                                              C.POINTER(GroundStats), C.POINTER(C.c_float)]
         _LIB = L
     return _LIB
 
@@ -503,6 +513,63 @@ class Context:
                                             C.c_void_p(labels.ctypes.data), C.byref(st)), "wm_ground_segment")
         stats = {k: getattr(st, k) for k, _ in GroundStats._fields_}
         return labels[:n].copy(), idx[:m.value].copy(), stats
+
+    def ground_segment_batch(self, clouds, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING, points=False):
+        """The filter for a queue of scans in one device call (wm_ground_segment_batch) -> [(labels, indices,
+        stats), ...], each as ground_segment's for that scan alone.  `clouds`: float32 (n, 3|4) numpy arrays or HIP
+        torch tensors (separate allocations are fine), all of one kind; one `params` and one `keep` for the batch.
+        points=True: -> (that list, kept, offsets) with `kept` the kept points of all scans, (m, 3|4) float32 in
+        output order, scan k's at kept[offsets[k]:offsets[k + 1]] -- for device inputs a device tensor whose slices
+        icp_batch_match takes as they are, for host inputs a numpy array."""
+        n_scans = len(clouds)
+        p = params if isinstance(params, GroundParams) else ground_params(params)
+        scans = (GroundScan * max(n_scans, 1))()
+        alive, stride, mem, sizes = [], None, None, []
+        for k, cloud in enumerate(clouds):
+            ptr, n, sk, mk, a = _cloud_arg(cloud)
+            assert stride in (None, sk) and mem in (None, mk), "the scans of a batch share one layout and one memory"
+            stride, mem = sk, mk
+            alive.append(a)
+            scans[k].pts, scans[k].n = ptr, n
+            sizes.append(n)
+        stride, mem = stride or 12, WM_MEM_HOST if mem is None else mem
+        total = sum(sizes)
+        offs = (C.c_size_t * (n_scans + 1))()
+        st = (GroundStats * max(n_scans, 1))()
+        labels = np.zeros(max(total, 1), np.uint8)
+        idx = np.empty(max(total, 1), np.int32)
+        on_device = points and mem == WM_MEM_DEVICE
+        kept = None
+        if on_device:  # everything the call writes lives on the device; labels and indices are fetched afterwards
+            import torch
+            dev = alive[0].device if alive else "cuda"
+            kept = torch.empty((max(total, 1), stride // 4), dtype=torch.float32, device=dev)
+            d_idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+            d_lab = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()  # (the context's stream is not torch's)
+            where = (d_idx.data_ptr(), kept.data_ptr(), stride, WM_MEM_DEVICE, d_lab.data_ptr())
+        elif points:
+            kept = np.empty((max(total, 1), stride // 4), np.float32)
+            where = (idx.ctypes.data, kept.ctypes.data, stride, WM_MEM_HOST, labels.ctypes.data)
+        else:
+            where = (idx.ctypes.data, None, 0, WM_MEM_HOST, labels.ctypes.data)
+        idx_p, pts_p, out_stride, out_mem, lab_p = where
+        self._check(lib().wm_ground_segment_batch(self._h, scans, n_scans, stride, mem, C.byref(p), int(keep),
+                                                  C.c_void_p(idx_p), total, C.c_void_p(pts_p), out_stride, out_mem,
+                                                  offs, C.c_void_p(lab_p), st, None),
+                    "wm_ground_segment_batch")
+        if on_device:
+            idx = d_idx.cpu().numpy()
+            labels = d_lab.cpu().numpy() if total else labels
+        offsets = np.array(list(offs), np.int64)
+        out, at = [], 0
+        for k in range(n_scans):
+            stats = {name: getattr(st[k], name) for name, _ in GroundStats._fields_}
+            out.append((labels[at:at + sizes[k]].copy(), idx[offsets[k]:offsets[k + 1]].copy(), stats))
+            at += sizes[k]
+        if not points:
+            return out
+        return out, kept[:offsets[-1]], offsets
 
     def voxel_downsample(self, cloud, leaf):
         ptr, n, stride, mem, keep = _cloud_arg(cloud)

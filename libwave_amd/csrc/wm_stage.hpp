@@ -1,7 +1,8 @@
 // wm_stage.hpp -- how a batch of pairs gets to the device and its results back: the one staging
-// sequence of wm_icp_batch_match, wm_gicp_batch_match, wm_ndt_batch_match and the batched voxel filter
+// sequence of wm_icp_batch_match, wm_gicp_batch_match, wm_ndt_batch_match, the batched voxel filter and
+// wm_ground_segment_batch (whose table rows are scans, not pairs: the helper does not look into a row)
 // (the structs: wm_internal.hpp, where the context holds them).  On the context's stream, in this order:
-// the host clouds in slices, the pair table, ev_a, the caller's kernels, ev_b, the outputs.
+// the host clouds in slices, the table, ev_a, the caller's kernels, ev_b, the outputs.
 #pragma once
 #include <string.h>
 
