@@ -262,17 +262,18 @@ int wm_debug_bins_sum(const double *x, size_t n, const unsigned *perm, double *o
  * order and the voxel filter are built on above 256k points) on HOST arrays: values_out[i] = the input position of the
  * i-th pair in ascending order of the low `bits` bits of the key (equal keys in input order).  key_bytes: 4 or 8. */
 int wm_debug_sort_pairs(wm_ctx *ctx, const void *keys, int key_bytes, size_t n, unsigned bits, unsigned *values_out);
-/* Tuning knobs by name (tests, benchmarks; the defaults are the product's): "cert_from" (-1: the
- * certificate kernel takes over once an ICP step is small, -2: never, k >= 0: from iteration k of
- * every align), "cert_disp" (that step size, in level-0 grid cells), "cert_pad_mul",
- * "cert_pad_frac", "cert_nb", "gicp_served" (0 / 1 / 2: GICP's objective evaluations launched / served by the
- * resident evaluator / served without the on-chip pair cache), "late" (1: the late ICP iterations -- certificate,
- * searches, sums, solve, stopping rules -- in ONE resident launch, k_nn_cert<.., LATE> + k_late_solver; 0, the
- * default: a launch per iteration, which measures the same or faster), "bins" (0: an ICP iteration's sums as rows
- * of partial sums and a reduction launch; 1, the default: as exact integer limbs in bins), "ndt_vox_split" (NDT model:
- * the points per voxel up to which a lane, not a wave, forms a voxel's sums; -1: the library's choice) and "ndt_keys64"
- * (1: 64-bit voxel sort keys whatever the lattice's size) -- both rebuild the model at the next NDT call.  None of them
- * changes a result.  WM_ERR_ARG for an unknown name. */
+/* Tuning knobs by name (tests, benchmarks; the defaults are the product's).  Each is also read from the environment
+ * when a context is created (mostly WM_TUNE_<NAME>; INTEGRATION.md lists them all).  Among them: "cert_from"
+ * (-1: the certificate kernel takes over once an ICP step is small, -2: never, k >= 0: from iteration k of every
+ * align), "cert_disp" (that step size, in level-0 grid cells), "cert_pad_mul", "cert_pad_frac", "gicp_served"
+ * (0 / 1 / 2: GICP's objective evaluations launched / served by the resident evaluator / served without the on-chip
+ * pair cache), "late" (1: the late ICP iterations -- certificate, searches, sums, solve, stopping rules -- in ONE
+ * resident launch, k_nn_cert<.., LATE> + k_late_solver; 0, the default: a launch per iteration, which measures the
+ * same or faster), "bins" (0: an ICP iteration's sums as rows of partial sums and a reduction launch; 1, the default:
+ * as exact integer limbs in bins), "ndt_vox_split" (NDT model: the points per voxel up to which a lane, not a wave,
+ * forms a voxel's sums; -1: the library's choice) and "ndt_keys64" (1: 64-bit voxel sort keys whatever the lattice's
+ * size) -- both rebuild the model at the next NDT call.  None of them changes a result.  WM_ERR_ARG for an unknown
+ * name or a value outside the knob's range. */
 int wm_set_option(wm_ctx *ctx, const char *name, double value);
 /* developer: out == NULL arms a log of `iterations` launches (0 disarms); otherwise writes, per
  * launch of the certificate kernel since, how many queries it had to search; returns the count */

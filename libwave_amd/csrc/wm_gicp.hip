@@ -57,22 +57,18 @@ __global__ void __launch_bounds__(kCovBlock) __attribute__((amdgpu_waves_per_eu(
     if (i >= n) return;
     const float4 q = qpts[i];
     const unsigned slot = (by_w & 1) ? __float_as_uint(q.w) : i;
-    double *out = cov_out + (size_t) slot * 9;
     if (!(q.x == q.x)) {  // non-finite point: never matched; keep a defined value
+        double *out = cov_out + (size_t) slot * 9;
 #pragma unroll
         for (int a = 0; a < 9; ++a) out[a] = (a % 4 == 0) ? 1.0 : 0.0;
         return;
     }
     unsigned long long best[K];
-    // (developer timing experiment, WM_TUNE_COV_DBG -- WRONG results: 512 = no neighbour search, 256 = no SVD.
-    // Measured at 500k points: 329 us as is, 314 without the SVD, 49 without the search, 27 without both:
-    // the k-NN search is 85 % of this kernel)
-    if (by_w & 512) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) best[j] = (unsigned long long) min(i + (unsigned) j, n - 1u);
-    } else
+    // (measured at 500k points: 329 us, of which the k-NN search is 85 %: 314 without the SVD, 49 without the search)
     knn_search<K>(g, q.x, q.y, q.z, k, r0_cells, best, s_runs, threadIdx.x, kCovBlock);
-    gicp_cov_of_list<K>(best, k, eps, [&](unsigned idx) { return orig[idx]; }, out, (by_w & 256) != 0);
+    // (the output address is formed here, not before the search: two registers less across it, which keeps the
+    // K = 8 instantiation free of spills at its 80)
+    gicp_cov_of_list<K>(best, k, eps, [&](unsigned idx) { return orig[idx]; }, cov_out + (size_t) slot * 9);
 }
 
 
@@ -599,7 +595,7 @@ static void serve_post(wm_ctx *ctx, const FdfArgs *A, unsigned cmd) {
 static void serve_begin(GicpFn &F) {
     wm_ctx *ctx = F.ctx;
     F.served = false;
-    if (!ctx->tune_gicp_served || ctx->gicp_profile || getenv("WM_GICP_TRACE")) return;
+    if (!ctx->tune_gicp_served || ctx->gicp_profile || !ctx->gicp_trace_path.empty()) return;
     if (ctx->device < 0 || ctx->device >= 64) return;
     if (ctx->gicp_serve_ok < 0) return;
     if (ctx->gicp_serve_ok == 0) {  // first use: is device memory host-writable, and does the grid fit?
@@ -659,7 +655,7 @@ static void serve_begin(GicpFn &F) {
         resident_release(ctx->device, share);
         return;
     }
-    unsigned long long *dbg = getenv("WM_GICP_SERVE_DEBUG") ? (unsigned long long *) ((char *) ctx->gicp_mailbox.p + 256) : nullptr;
+    unsigned long long *dbg = ctx->gicp_serve_debug ? (unsigned long long *) ((char *) ctx->gicp_mailbox.p + 256) : nullptr;
     if (ctx->gicp_serve_cached && ctx->tune_gicp_served != 2)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_fdf_served<kServeCached>), dim3(nb), dim3(kBlock),
                            (size_t) kServeCached * 9 * kBlock * sizeof(double), ctx->stream, ctx->src_sorted.as<float4>(),
@@ -691,7 +687,7 @@ static void serve_end(GicpFn &F) {
         if (ab && ctx->trace) fprintf(stderr, "[wm] gicp: resident evaluator abandoned a round (guard / late workgroups)\n");
         ctx->gicp_serve_abandoned += ab ? 1 : 0;
     }
-    if (getenv("WM_GICP_SERVE_DEBUG")) {  // developer: device-side stamps of the first rounds (100 MHz ticks)
+    if (ctx->gicp_serve_debug) {  // developer: device-side stamps of the first rounds (100 MHz ticks)
         unsigned long long d[64 * 4];
         if (hipMemcpy(d, (char *) ctx->gicp_mailbox.p + 256, sizeof(d), hipMemcpyDeviceToHost) == hipSuccess) {
             for (unsigned r = 0; r < F.served_evals && r < 24; ++r)
@@ -785,8 +781,8 @@ static double gicp_fdf(GicpFn &F, const double x[6], double g[6]) {
         for (int k = 0; k < 9; ++k) Racc[k] = a[4 + k] * 2.0 / m;
         r_derivative(x, Racc, g);
     }
-    if (const char *path = getenv("WM_GICP_TRACE")) {  // developer: every evaluation, in hex floats
-        if (FILE *fp = fopen(path, "a")) {
+    if (!ctx->gicp_trace_path.empty()) {  // developer: every evaluation, in hex floats
+        if (FILE *fp = fopen(ctx->gicp_trace_path.c_str(), "a")) {
             fprintf(fp, "%d", F.m);
             for (int k = 0; k < 6; ++k) fprintf(fp, " %.17g", x[k]);
             fprintf(fp, " | %.17g |", a[0] / m);
@@ -806,6 +802,7 @@ struct GicpQuadFn {
     double Q[kQuadN];
     float T0[12];
     const double *base;
+    const char *trace_path = nullptr;  // developer (WM_GICP_TRACE)
     int m = 0;
     int evals = 0;
     int pairs() const { return m; }
@@ -814,8 +811,8 @@ struct GicpQuadFn {
     double fdf(const double x[6], double g[6]) {
         ++evals;
         const double f = gicp_quad_eval(Q, T0, base, x, g);
-        if (const char *path = getenv("WM_GICP_TRACE")) {  // developer: every evaluation (as gicp_fdf prints them)
-            if (FILE *fp = fopen(path, "a")) {
+        if (trace_path) {  // developer: every evaluation (as gicp_fdf prints them)
+            if (FILE *fp = fopen(trace_path, "a")) {
                 fprintf(fp, "%d", m);
                 for (int k = 0; k < 6; ++k) fprintf(fp, " %.17g", x[k]);
                 fprintf(fp, " | %.17g |", f);
@@ -866,7 +863,7 @@ static int launch_cov(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, 
                       int k, double eps, double *out, int by_w) {
     if (n == 0) return WM_OK;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gicp_cov<K>), dim3((unsigned) ((n + kCovBlock - 1) / kCovBlock)),
-                       dim3(kCovBlock), 0, ctx->stream, g, q, (unsigned) n, orig, k, eps, out, by_w | ctx->tune_cov_dbg,
+                       dim3(kCovBlock), 0, ctx->stream, g, q, (unsigned) n, orig, k, eps, out, by_w,
                        ctx->tune_knn_r0 > 0 ? ctx->tune_knn_r0 : (k <= 12 ? 1.0f : 1.5f));
     WM_HIP(ctx, hipGetLastError());
 #ifdef WM_COV_COUNT
@@ -906,7 +903,7 @@ static int compute_covariances(wm_ctx *ctx, int k, double eps) {
         // target: neighbours from the level-0 search grid
         if (!ctx->levels[0].built) WM_TRY(ensure_levels(ctx, -1.0));
         WM_HIP(ctx, ctx->gicp_c2.reserve((ctx->n_tgt_input > 0 ? ctx->n_tgt_input : 1) * 9 * sizeof(double)));
-        if (ctx->tune_two_streams && ctx->side_stream && !(ctx->gicp_cov_src_valid && same)) {
+        if (ctx->side_stream && !(ctx->gicp_cov_src_valid && same)) {
             WM_HIP(ctx, hipEventRecord(ctx->ev_fork, main_stream));
             WM_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
             ctx->stream = ctx->side_stream;
@@ -1035,6 +1032,7 @@ int wm_gicp_align(wm_ctx *ctx, const wm_gicp_params *prm, double T_out[16], wm_g
     const bool statistics = prm->objective != WM_GICP_OBJECTIVE_PCL_SUMS;
     GicpQuadFn Q;
     Q.base = base;
+    Q.trace_path = ctx->gicp_trace_path.empty() ? nullptr : ctx->gicp_trace_path.c_str();
     const int max_it = prm->force_iterations > 0 ? prm->force_iterations : prm->max_iter;
     int iter = 0, inner_total = 0;
     bool converged = false;
@@ -1147,6 +1145,7 @@ int wm_gicp_eval(wm_ctx *ctx, const wm_gicp_params *prm, const double T_pair[16]
         mat4_identity(base);
         GicpQuadFn Q;
         Q.base = base;
+        Q.trace_path = ctx->gicp_trace_path.empty() ? nullptr : ctx->gicp_trace_path.c_str();
         float Tf[16];
         for (int i = 0; i < 16; ++i) Tf[i] = (float) T_pair[i];
         WM_TRY(gicp_quad_statistics(ctx, Tf, Q, nullptr));

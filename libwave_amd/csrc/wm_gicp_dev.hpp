@@ -218,10 +218,10 @@ __device__ void knn_search(const GridDev &g, float qx, float qy, float qz, int k
 
 // the covariance PCL's computeCovariances gives a point from its k nearest neighbours (best[0 .. k-1], keys of
 // (d2, index); fetch(index) = the neighbour's coordinates): float products into double sums, 3x3 SVD, spectrum
-// replaced by (1, 1, eps).  no_svd: developer timing experiment (the raw covariance goes out).
+// replaced by (1, 1, eps).
 template <int K, class Fetch>
 __device__ __forceinline__ void gicp_cov_of_list(const unsigned long long (&best)[K], int k, double eps, Fetch fetch,
-                                                 double *__restrict__ out, bool no_svd = false) {
+                                                 double *__restrict__ out) {
     double mean[3] = {0, 0, 0}, c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int j = 0; j < K; ++j) {
@@ -251,11 +251,6 @@ __device__ __forceinline__ void gicp_cov_of_list(const unsigned long long (&best
                 c[b * 3 + a] = c[a * 3 + b];
             }
     double U[9], S[3], V[9];
-    if (no_svd) {
-#pragma unroll
-        for (int a = 0; a < 9; ++a) out[a] = c[a];
-        return;
-    }
     svd3<false>(c, U, S, V);  // IEEE operations only: the oracle reproduces these matrices bit for bit
 #pragma unroll
     for (int a = 0; a < 3; ++a)

@@ -809,7 +809,7 @@ static int gicp_small_run(wm_ctx *ctx, const PairJob *jobs, int n, size_t stride
     // 1: trace.  Bits 2 / 4 are timing experiments that give WRONG registrations (no Mahalanobis matrices / no
     // search): they exist only in a developer build (-DWM_GICP_SMALL_EXPERIMENTS); a stray environment variable
     // must not be able to switch them on in the production library
-    P.debug = getenv("WM_GICP_SMALL_TRACE") ? atoi(getenv("WM_GICP_SMALL_TRACE")) : 0;
+    P.debug = ctx->gicp_small_trace;
 #ifndef WM_GICP_SMALL_EXPERIMENTS
     P.debug &= 1;
 #endif

@@ -90,7 +90,7 @@ int pack_cloud(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, f
         dptr = static_cast<const unsigned char *>(pts);
     }
     unsigned blocks = (unsigned) ((n + kBlock - 1) / kBlock);
-    if (bbox_partials && bbox_blocks && ctx->tune_pack_bbox) {  // (the cloud's box in the same launch: k_bbox<true>)
+    if (bbox_partials && bbox_blocks) {  // (the cloud's box in the same launch: k_bbox<true>)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bbox<true>), dim3(*bbox_blocks), dim3(kBlock), 0, ctx->stream, out, n, bbox_partials, dptr, stride);
         WM_HIP(ctx, hipGetLastError());
         return WM_OK;
@@ -305,124 +305,32 @@ __global__ void __launch_bounds__(kBlock) k_scatter(const float4 *pts, size_t n,
 }
 
 // ------------------------------------------------------- exclusive scan
-constexpr int kScanItems = 8;
-constexpr int kScanTile = kBlock * kScanItems;  // 2048
-
-__device__ inline unsigned block_exclusive_scan(unsigned v, unsigned *total, unsigned *lds) {
-    // wave-level inclusive scan
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        unsigned t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    unsigned base = 0, tot = 0;
-    for (int w = 0; w < kBlock / 64; ++w) {
-        unsigned s = lds[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-// pass 1: per-tile local exclusive scan (in place into out) + tile sums
-__global__ void __launch_bounds__(kBlock) k_scan_tiles(const unsigned *in, size_t n, unsigned *out,
-                                                        unsigned *tile_sums) {
-    __shared__ unsigned lds[kBlock / 64];
-    size_t base = (size_t) blockIdx.x * kScanTile + (size_t) threadIdx.x * kScanItems;
-    unsigned v[kScanItems], sum = 0;
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        v[k] = (base + k < n) ? in[base + k] : 0u;
-        sum += v[k];
-    }
-    unsigned total;
-    unsigned ex = block_exclusive_scan(sum, &total, lds);
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < n) out[base + k] = ex;
-        ex += v[k];
-    }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// pass 2: single block scans the tile sums (exclusive), carries across chunks
-__global__ void __launch_bounds__(kBlock) k_scan_sums(unsigned *tile_sums, size_t ntiles,
-                                                       unsigned *grand_total) {
-    __shared__ unsigned lds[kBlock / 64];
-    __shared__ unsigned carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (size_t c0 = 0; c0 < ntiles; c0 += kBlock) {
-        size_t i = c0 + threadIdx.x;
-        unsigned v = (i < ntiles) ? tile_sums[i] : 0u;
-        unsigned total;
-        unsigned ex = block_exclusive_scan(v, &total, lds);
-        unsigned carry = carry_s;
-        if (i < ntiles) tile_sums[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *grand_total = carry_s;
-}
-
-// pass 3: add tile offsets; also writes out[n] = grand total
-__global__ void __launch_bounds__(kBlock) k_scan_add(unsigned *out, size_t n,
-                                                      const unsigned *tile_sums,
-                                                      const unsigned *grand_total) {
-    size_t base = (size_t) blockIdx.x * kScanTile + (size_t) threadIdx.x * kScanItems;
-    unsigned add = tile_sums[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k)
-        if (base + k < n) out[base + k] += add;
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = *grand_total;
-}
-
 struct ScanIn {  // in[i] for i < n, 0 at i = n (exclusive_scan below)
     const unsigned *in;
     size_t n;
     __device__ unsigned operator()(size_t i) const { return i < n ? in[i] : 0u; }
 };
 
-// out must hold n+1 entries (out[n] = the total).  rocPRIM's single-pass look-back scan: 5 M cell counts in ~17 us against 41 us for the three-kernel
-// tiles / tile sums / add scan above (kept for `WM_TUNE_SCAN=0`).
+// out must hold n+1 entries (out[n] = the total).  rocPRIM's single-pass look-back scan: 5 M cell counts in ~17 us
+// (a three-kernel tiles / tile sums / add scan took 41 us).
 int exclusive_scan(wm_ctx *ctx, const unsigned *in, size_t n, unsigned *out) {
     if (n == 0) {
         WM_HIP(ctx, hipMemsetAsync(out, 0, sizeof(unsigned), ctx->stream));
         return WM_OK;
     }
-    if (ctx->tune_scan) {
-        // n + 1 items through an iterator that reads in[i] below n and 0 at n: out[n] comes out as the
-        // total, without a one-thread kernel behind the scan (a dependent launch of its own: ~5 us)
-        auto it = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), ScanIn{in, n});
-        // (32 items per thread: 54 us for the 14 M cell counts of a 1M-point level 0 against 67 with rocPRIM's default
-        // tuning; 17 against 19 at 2 M -- scripts/dev/scan_probe.hip)
-        using scan_cfg = rocprim::scan_config<256, 32, rocprim::block_load_method::block_load_transpose,
-                                              rocprim::block_store_method::block_store_transpose,
-                                              rocprim::block_scan_algorithm::using_warp_scan>;
-        size_t bytes = 0;
-        WM_HIP(ctx, rocprim::exclusive_scan<scan_cfg>(nullptr, bytes, it, out, 0u, n + 1, rocprim::plus<unsigned>(),
-                                                      ctx->stream));
-        WM_HIP(ctx, ctx->block_sums.reserve(bytes + 64));
-        WM_HIP(ctx, rocprim::exclusive_scan<scan_cfg>(ctx->block_sums.p, bytes, it, out, 0u, n + 1,
-                                                      rocprim::plus<unsigned>(), ctx->stream));
-        WM_HIP(ctx, hipGetLastError());
-        return WM_OK;
-    }
-    size_t ntiles = (n + kScanTile - 1) / kScanTile;
-    WM_HIP(ctx, ctx->block_sums.reserve((ntiles + 2) * sizeof(unsigned)));
-    unsigned *sums = ctx->block_sums.as<unsigned>();
-    unsigned *grand = sums + ntiles;
-    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned) ntiles), dim3(kBlock), 0, ctx->stream, in, n,
-                       out, sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, ctx->stream, sums, ntiles, grand);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned) ntiles), dim3(kBlock), 0, ctx->stream, out, n,
-                       sums, grand);
+    // n + 1 items through an iterator that reads in[i] below n and 0 at n: out[n] comes out as the
+    // total, without a one-thread kernel behind the scan (a dependent launch of its own: ~5 us)
+    auto it = rocprim::make_transform_iterator(rocprim::counting_iterator<size_t>(0), ScanIn{in, n});
+    // (32 items per thread: 54 us for the 14 M cell counts of a 1M-point level 0 against 67 with rocPRIM's default
+    // tuning; 17 against 19 at 2 M -- scripts/dev/scan_probe.hip)
+    using scan_cfg = rocprim::scan_config<256, 32, rocprim::block_load_method::block_load_transpose,
+                                          rocprim::block_store_method::block_store_transpose,
+                                          rocprim::block_scan_algorithm::using_warp_scan>;
+    size_t bytes = 0;
+    WM_HIP(ctx, rocprim::exclusive_scan<scan_cfg>(nullptr, bytes, it, out, 0u, n + 1, rocprim::plus<unsigned>(), ctx->stream));
+    WM_HIP(ctx, ctx->block_sums.reserve(bytes + 64));
+    WM_HIP(ctx, rocprim::exclusive_scan<scan_cfg>(ctx->block_sums.p, bytes, it, out, 0u, n + 1, rocprim::plus<unsigned>(),
+                                                  ctx->stream));
     WM_HIP(ctx, hipGetLastError());
     return WM_OK;
 }
@@ -573,10 +481,10 @@ int morton_sort(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, size_t
                        key, 1u << (3 * bits), k1, v1);
     size_t tmp_bytes = 0;
     WM_HIP(ctx, sort_pairs_low_bits(nullptr, tmp_bytes, k1, k2, v1, v2, n, 3 * bits + 1, ctx->stream,
-                                    (size_t) ctx->tune_radix_min, ctx->tune_sort));
+                                    (size_t) ctx->tune_radix_min));
     WM_HIP(ctx, ctx->vg_tmp.reserve(tmp_bytes));
     WM_HIP(ctx, sort_pairs_low_bits(ctx->vg_tmp.p, tmp_bytes, k1, k2, v1, v2, n, 3 * bits + 1, ctx->stream,
-                                    (size_t) ctx->tune_radix_min, ctx->tune_sort));
+                                    (size_t) ctx->tune_radix_min));
     const unsigned gblocks = (unsigned) ((n_valid + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_gather, dim3(gblocks), dim3(kBlock), 0, ctx->stream, pts, v2,
                        (unsigned) n_valid, out);

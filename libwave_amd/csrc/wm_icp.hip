@@ -557,17 +557,6 @@ static int launch_reduce_solve(wm_ctx *ctx, unsigned rows, double *stats_io, uns
     return WM_OK;
 }
 
-// one iteration's correspondence search + statistics on the grid: fused (the search kernel leaves
-// the partial rows) or as two passes; *rows = partial rows to add up
-static int launch_search_and_stats(wm_ctx *ctx, float thr, int mode, hipEvent_t e0, hipEvent_t e1,
-                                   hipEvent_t e1b, unsigned *rows, bool use_bins = false) {
-    if (ctx->tune_fuse_stats) return launch_nn_grid(ctx, thr, e0, e1, e1b, mode, rows, use_bins);
-    WM_TRY(launch_nn_grid(ctx, thr, e0, e1, e1b));
-    WM_TRY(launch_stats(ctx, mode));
-    *rows = (unsigned) stat_blocks(ctx->n_src);
-    return WM_OK;
-}
-
 static int prepare_work(wm_ctx *ctx) {
     const size_t n = ctx->n_src > 0 ? ctx->n_src : 1;
     WM_HIP(ctx, ctx->keys.reserve(n * sizeof(unsigned long long)));
@@ -940,8 +929,8 @@ int finalize_clouds(wm_ctx *ctx, double max_corr, int nn_method, int sort_aside)
     if (sort_src) ctx->n_src = src_valid;  // (the count of finite points: what the sort will leave in src_sorted)
     hipStream_t main_stream = ctx->stream;
     // the Morton sort of the source is independent of the target's grid build: side stream
-    const bool aside = sort_aside != 0 && sort_src && ctx->tune_two_streams && ctx->side_stream != nullptr;
-    const bool side = aside || (sort_src && ctx->tune_two_streams && ctx->side_stream && tgt_new && max_corr > 0);
+    const bool aside = sort_aside != 0 && sort_src && ctx->side_stream != nullptr;
+    const bool side = aside || (sort_src && ctx->side_stream && tgt_new && max_corr > 0);
     if (side) {  // (the sort may start as soon as what is on the main stream NOW -- the packed clouds -- is done)
         WM_HIP(ctx, hipEventRecord(ctx->ev_fork, main_stream));
         WM_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
@@ -995,6 +984,70 @@ const char *wm_strerror(int s) {
 
 const char *wm_last_error(const wm_ctx *ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
+// ---- options: every knob of a context, by wm_set_option's name and by the environment variable read at wm_ctx_create.
+// An integer or a float field, the closed range [lo, hi] of accepted values, and:
+//   kOpenLo    the range is (lo, hi]
+//   kFlag      any non-zero value means 1 -- except the top of the range, which is kept (gicp_served's 2)
+//   kNdtModel  the NDT voxel model depends on it and is rebuilt
+namespace {
+enum : unsigned { kOpenLo = 1u, kFlag = 2u, kNdtModel = 4u };
+struct Option {
+    const char *name, *env;
+    int wm_ctx::*i;
+    float wm_ctx::*f;
+    double lo, hi;
+    unsigned flags;
+};
+constexpr double kIntMin = -2147483648.0, kIntMax = 2147483647.0, kFloatMax = 3.0e38;
+const Option kOptions[] = {
+    // the grid search (wm_nn.hip)
+    {"lane_lf", "WM_TUNE_LANE_LF", nullptr, &wm_ctx::tune_lane_lf, 0, kFloatMax, kOpenLo},
+    {"coop_lf", "WM_TUNE_COOP_LF", nullptr, &wm_ctx::tune_coop_lf, 0, kFloatMax, kOpenLo},
+    {"r0", "WM_TUNE_R0", nullptr, &wm_ctx::tune_r0, 0, kFloatMax, kOpenLo},
+    {"r_light", "WM_TUNE_R_LIGHT", nullptr, &wm_ctx::tune_r_light, 0, kFloatMax, kOpenLo},
+    {"xcd_chunk", "WM_TUNE_XCD_CHUNK", &wm_ctx::tune_xcd_chunk, nullptr, kIntMin, kIntMax, 0},
+    {"nn_balanced", "WM_TUNE_NN_BALANCED", &wm_ctx::tune_nn_balanced, nullptr, kIntMin, kIntMax, 0},
+    // the ICP loop and its certificate kernel (wm_icp.hip)
+    {"lag", "WM_TUNE_LAG", &wm_ctx::tune_lag, nullptr, 1, 16, 0},
+    {"spin_us", "WM_TUNE_SPIN_US", &wm_ctx::tune_spin_us, nullptr, kIntMin, kIntMax, 0},
+    {"cert_from", "WM_TUNE_CERT_FROM", &wm_ctx::tune_cert_from, nullptr, kIntMin, kIntMax, 0},
+    {"cert_disp", "WM_TUNE_CERT_DISP", nullptr, &wm_ctx::tune_cert_disp, 0, kFloatMax, kOpenLo},
+    {"cert_changed", "WM_TUNE_CERT_CHANGED", nullptr, &wm_ctx::tune_cert_changed, 0, kFloatMax, kOpenLo},
+    {"cert_unsettled", "WM_TUNE_CERT_UNSETTLED", nullptr, &wm_ctx::tune_cert_unsettled, 0, kFloatMax, kOpenLo},
+    {"cert_pad_mul", "WM_TUNE_CERT_PAD_MUL", nullptr, &wm_ctx::tune_cert_pad_mul, 0, kFloatMax, 0},
+    {"cert_pad_frac", "WM_TUNE_CERT_PAD_FRAC", nullptr, &wm_ctx::tune_cert_pad_frac, 0, kFloatMax, 0},
+    {"late", "WM_TUNE_LATE", &wm_ctx::tune_late, nullptr, kIntMin, kIntMax, kFlag},
+    {"bins", "WM_TUNE_BINS", &wm_ctx::tune_bins, nullptr, kIntMin, kIntMax, 0},
+    {"early_source", "WM_TUNE_EARLY_SOURCE", &wm_ctx::tune_early_source, nullptr, kIntMin, kIntMax, 0},
+    {"shard_force", "WM_SHARD_FORCE", &wm_ctx::tune_force_shard, nullptr, kIntMin, kIntMax, 0},
+    {"trace", "WM_TRACE", &wm_ctx::trace, nullptr, kIntMin, kIntMax, kFlag},
+    // GICP (wm_gicp.hip)
+    {"gicp_served", "WM_TUNE_GICP_SERVED", &wm_ctx::tune_gicp_served, nullptr, kIntMin, 2, kFlag},
+    {"gicp_serve_test_stall_ms", "WM_TUNE_GICP_SERVE_TEST_STALL_MS", &wm_ctx::gicp_serve_test_stall_ms, nullptr, kIntMin, kIntMax, 0},
+    {"gicp_blocks", "WM_TUNE_GICP_BLOCKS", &wm_ctx::tune_gicp_blocks, nullptr, 1, 4096, 0},
+    {"knn_r0", "WM_TUNE_KNN_R0", nullptr, &wm_ctx::tune_knn_r0, 0.25, 8, 0},
+    {"gicp_profile", "WM_GICP_PROFILE", &wm_ctx::gicp_profile, nullptr, kIntMin, kIntMax, kFlag},
+    // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
+    {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
+    {"ndt_dense", "WM_TUNE_NDT_DENSE", &wm_ctx::tune_ndt_dense, nullptr, kIntMin, kIntMax, 0},
+    {"ndt_vox_split", "WM_TUNE_NDT_VOX_SPLIT", &wm_ctx::tune_ndt_vox_split, nullptr, kIntMin, kIntMax, kNdtModel},
+    {"ndt_keys64", "WM_TUNE_NDT_KEYS64", &wm_ctx::tune_ndt_keys64, nullptr, kIntMin, kIntMax, kFlag | kNdtModel},
+    {"ndt_blocks", "WM_TUNE_NDT_BLOCKS", &wm_ctx::tune_ndt_blocks, nullptr, 0, 4096, 0},
+    {"ndt_spec_hessian", "WM_TUNE_NDT_SPEC_HESSIAN", &wm_ctx::tune_ndt_spec_hessian, nullptr, kIntMin, kIntMax, 0},
+    {"ndt_fused_fetch", "WM_TUNE_NDT_FUSED_FETCH", &wm_ctx::tune_ndt_fused_fetch, nullptr, kIntMin, kIntMax, 0},
+    {"ndt_profile", "WM_NDT_PROFILE", &wm_ctx::ndt_profile, nullptr, kIntMin, kIntMax, kFlag},
+};
+
+int apply_option(wm_ctx *ctx, const Option &o, double v) {
+    if ((o.flags & kFlag) && v != o.hi) v = v != 0 ? 1 : 0;
+    if (!(v >= o.lo && v <= o.hi) || ((o.flags & kOpenLo) && v == o.lo)) return WM_ERR_ARG;
+    if (o.i) ctx->*o.i = (int) v;
+    else ctx->*o.f = (float) v;
+    if (o.flags & kNdtModel) ctx->ndt_built = false;
+    return WM_OK;
+}
+}  // namespace
+
 int wm_ctx_create(wm_ctx **out, int device) {
     if (!out) return WM_ERR_ARG;
     *out = nullptr;
@@ -1013,88 +1066,14 @@ int wm_ctx_create(wm_ctx **out, int device) {
         return WM_ERR_HIP;
     }
     ctx->stream = ctx->own_stream;
-    if (const char *e = getenv("WM_TUNE_NDT_DENSE")) ctx->tune_ndt_dense = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NDT_VOX_SPLIT")) ctx->tune_ndt_vox_split = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NDT_KEYS64")) ctx->tune_ndt_keys64 = atoi(e);
-    if (const char *e = getenv("WM_TUNE_KNN_R0")) {
-        const float v = (float) atof(e);
-        if (v >= 0.25f && v <= 8.f) ctx->tune_knn_r0 = v;
-    }
-    if (const char *e = getenv("WM_TUNE_SPIN_US")) ctx->tune_spin_us = atoi(e);
-    if (const char *e = getenv("WM_TUNE_XCD_REVERSE")) ctx->tune_xcd_reverse = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NN_WALK_FILTER")) ctx->tune_nn_walk_filter = atoi(e);
-    if (const char *e = getenv("WM_TUNE_SCAN")) ctx->tune_scan = atoi(e);
-    if (const char *e = getenv("WM_SHARD_FORCE")) ctx->tune_force_shard = atoi(e);
-    if (const char *e = getenv("WM_TUNE_TWO_STREAMS")) ctx->tune_two_streams = atoi(e);
-    if (const char *e = getenv("WM_TUNE_FUSE_STATS")) ctx->tune_fuse_stats = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NN_BALANCED")) ctx->tune_nn_balanced = atoi(e);
-    if (const char *e = getenv("WM_TUNE_FAST_SOLVE")) ctx->tune_fast_solve = atoi(e);
-    if (const char *e = getenv("WM_TUNE_CERT_FROM")) ctx->tune_cert_from = atoi(e);
-    if (const char *e = getenv("WM_TUNE_CERT_NB")) ctx->tune_cert_nb = atoi(e);
-    if (const char *e = getenv("WM_TUNE_CERT_RC")) ctx->tune_cert_rc = atoi(e);
-    if (const char *e = getenv("WM_TUNE_CERT_DBG_SKIP")) ctx->tune_cert_dbg_skip = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NN_EARLY_LOADS")) ctx->tune_nn_early_loads = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NN_NT_STORES")) ctx->tune_nn_nt_stores = atoi(e);
-    if (const char *e = getenv("WM_TUNE_CERT_DISP")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_cert_disp = v;
-    }
-    if (const char *e = getenv("WM_TUNE_CERT_CHANGED")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_cert_changed = v;
-    }
-    if (const char *e = getenv("WM_TUNE_CERT_UNSETTLED")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_cert_unsettled = v;
-    }
-    if (const char *e = getenv("WM_TUNE_CERT_PAD_MUL")) {
-        const float v = (float) atof(e);
-        if (v >= 0) ctx->tune_cert_pad_mul = v;
-    }
-    if (const char *e = getenv("WM_TUNE_CERT_PAD_FRAC")) {
-        const float v = (float) atof(e);
-        if (v >= 0) ctx->tune_cert_pad_frac = v;
-    }
-    if (const char *e = getenv("WM_TUNE_XCD_CHUNK")) ctx->tune_xcd_chunk = atoi(e);
-    if (const char *e = getenv("WM_TUNE_RADIX_MIN")) ctx->tune_radix_min = atoi(e);
-    if (const char *e = getenv("WM_TUNE_SORT")) ctx->tune_sort = atoi(e);
-    if (const char *e = getenv("WM_TUNE_PACK_BBOX")) ctx->tune_pack_bbox = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NDT_BLOCKS")) {
-        const int v = atoi(e);
-        if (v >= 0 && v <= 4096) ctx->tune_ndt_blocks = v;
-    }
-    if (const char *e = getenv("WM_TUNE_GICP_BLOCKS")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 4096) ctx->tune_gicp_blocks = v;
-    }
-    if (const char *e = getenv("WM_TRACE")) ctx->trace = atoi(e) != 0;
-    if (const char *e = getenv("WM_TUNE_LANE_LF")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_lane_lf = v;
-    }
-    if (const char *e = getenv("WM_GICP_PROFILE")) ctx->gicp_profile = atoi(e) != 0;
-    if (const char *e = getenv("WM_NDT_PROFILE")) ctx->ndt_profile = atoi(e) != 0;
-    if (const char *e = getenv("WM_TUNE_COOP_LF")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_coop_lf = v;
-    }
-    if (const char *e = getenv("WM_TUNE_GICP_SERVED")) ctx->tune_gicp_served = atoi(e) == 2 ? 2 : (atoi(e) != 0 ? 1 : 0);
-    if (const char *e = getenv("WM_TUNE_NDT_SPEC_HESSIAN")) ctx->tune_ndt_spec_hessian = atoi(e);
-    if (const char *e = getenv("WM_TUNE_NDT_FUSED_FETCH")) ctx->tune_ndt_fused_fetch = atoi(e);
-    if (const char *e = getenv("WM_TUNE_LAG")) ctx->tune_lag = atoi(e);
-    if (const char *e = getenv("WM_TUNE_LATE")) ctx->tune_late = atoi(e);
-    if (const char *e = getenv("WM_TUNE_BINS")) ctx->tune_bins = atoi(e);
-    if (const char *e = getenv("WM_TUNE_GRID_VARIANT")) ctx->tune_grid_variant = atoi(e);
-    if (const char *e = getenv("WM_TUNE_EARLY_SOURCE")) ctx->tune_early_source = atoi(e);
-    if (const char *e = getenv("WM_TUNE_COV_DBG")) ctx->tune_cov_dbg = atoi(e) & 768;
-    if (const char *e = getenv("WM_TUNE_R0")) {
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_r0 = v;
-    }
-    if (const char *e = getenv("WM_TUNE_R_LIGHT")) {  // developer tuning knob
-        const float v = (float) atof(e);
-        if (v > 0) ctx->tune_r_light = v;
-    }
+    for (const Option &o : kOptions)
+        if (const char *e = getenv(o.env)) (void) apply_option(ctx, o, atof(e));  // (a value out of range is ignored)
+    // developer instrumentation, armed from the environment only
+    if (const char *e = getenv("WM_LATE_DEBUG")) ctx->late_debug_iter = atoi(e) > 0 ? atoi(e) : 0;
+    if (getenv("WM_CERT_PROF")) ctx->cert_prof_on = true;
+    if (const char *e = getenv("WM_GICP_TRACE")) ctx->gicp_trace_path = e;
+    if (getenv("WM_GICP_SERVE_DEBUG")) ctx->gicp_serve_debug = true;
+    if (const char *e = getenv("WM_GICP_SMALL_TRACE")) ctx->gicp_small_trace = atoi(e);
     *out = ctx;
     return WM_OK;
 }
@@ -1289,7 +1268,7 @@ int wm_icp_align(wm_ctx *ctx, const wm_icp_params *p, double T_out[16], wm_icp_s
     mat4_identity(I);
     const double prev = (p->carry_state && ctx->prev_mse >= 0) ? ctx->prev_mse : DBL_MAX;
     init_state(ctx->h_state, I, p, prev);
-    ctx->h_state->svd_warm = ctx->tune_fast_solve ? 1 : 0;
+    ctx->h_state->svd_warm = 1;
     set_step_scale(ctx);
     WM_TRY(upload_state(ctx));
 
@@ -1331,7 +1310,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
     }
     // (nothing of an earlier align is in flight: each ends with a fetch of the state)
     memset(ctx->h_pub, 0, sizeof(unsigned long long) * (size_t) (max_it + 1));
-    const bool can_cert = !brute && ctx->tune_fuse_stats && ctx->tune_nn_balanced && ctx->tune_cert_from >= -1 &&
+    const bool can_cert = !brute && ctx->tune_nn_balanced && ctx->tune_cert_from >= -1 &&
                           ctx->n_tgt_input < (1u << 26) - 8u && !ctx->cost_log.p;
     volatile unsigned long long *pub = ctx->h_pub;
     bool cert_on = false, bounds_valid = false, seen_done = false;
@@ -1344,7 +1323,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
     ctx->cert_launches = 0;
     // the grid path adds its sums into bins (wm_bins.hpp) and solves from them -- k_bins_solve, or, sharded, the
     // k_reduce_solve that carries the exchange: no k_reduce_rows, no rows of partial sums
-    const bool use_bins = !brute && ctx->tune_fuse_stats && ctx->tune_bins != 0 && !ctx->cost_log.p;
+    const bool use_bins = !brute && ctx->tune_bins != 0 && !ctx->cost_log.p;
     if (use_bins) {
         WM_TRY(bins_ready(ctx));  // (zeroes them if the last loop left them dirty)
         ctx->bins_dirty = true;   // (until this loop has ended normally)
@@ -1475,7 +1454,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
                     return WM_ERR_STATE;
                 }
                 const int reason = (int) ((w >> 24) & 0xFFu), inside = (int) (w & 0xFFFFFFu);
-                if (getenv("WM_LATE_DEBUG")) {  // developer: the solver's stamps (100 MHz wall clock)
+                if (ctx->late_debug_iter >= 0) {  // developer (WM_LATE_DEBUG): the solver's stamps (100 MHz wall clock)
                     unsigned long long d[64 * 4];
                     (void) hipStreamSynchronize(ctx->stream);
                     if (hipMemcpy(d, (char *) ctx->late_ctl.p + late_ctl_bytes(), sizeof(d), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1486,7 +1465,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
                                     (d[k * 4 + 1] - d[k * 4]) * 0.01, (d[k * 4 + 2] - d[k * 4 + 1]) * 0.01,
                                     (d[k * 4 + 3] - d[k * 4 + 2]) * 0.01);
                         // the workers' stamps of iteration WM_LATE_DEBUG, relative to the solver's hand-out before it
-                        const int li = atoi(getenv("WM_LATE_DEBUG"));
+                        const int li = ctx->late_debug_iter;
                         std::vector<unsigned long long> wst((size_t) late_blocks * 8);
                         if (li >= 1 && li < inside && li < 64 && ctx->cert_prof.p &&
                             hipMemcpy(wst.data(), ctx->cert_prof.p, wst.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1572,7 +1551,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
                 was_cert[(size_t) it] = 1;
             }
         } else {
-            WM_TRY(launch_search_and_stats(ctx, thr, p->mode, e0, e1, e1b, &rows, use_bins));
+            WM_TRY(launch_nn_grid(ctx, thr, e0, e1, e1b, p->mode, &rows, use_bins));
             bounds_valid = false;
         }
         if (e2) WM_HIP(ctx, hipEventRecord(e2, ctx->stream));
@@ -1821,7 +1800,7 @@ int shard_begin(wm_ctx *ctx, const wm_icp_params *p, double x_lo, double x_hi, d
     double I[16];
     mat4_identity(I);
     init_state(ctx->h_state, I, p, prev_mse0);
-    ctx->h_state->svd_warm = ctx->tune_fast_solve ? 1 : 0;
+    ctx->h_state->svd_warm = 1;
     ctx->h_state->slab_on = 1;
     ctx->h_state->slab_lo = x_lo < -3.0e38 ? -INFINITY : (float) x_lo;
     ctx->h_state->slab_hi = x_hi > 3.0e38 ? INFINITY : (float) x_hi;
@@ -1874,7 +1853,7 @@ int wm_icp_shard_local_stats(wm_ctx *ctx, void *stats_dev) {
             WM_TRY(launch_stats(ctx, ctx->shard_params.mode));
             rows = (unsigned) stat_blocks(ctx->n_src);
         } else {
-            WM_TRY(launch_search_and_stats(ctx, ctx->shard_thr, ctx->shard_params.mode, e0, e1, nullptr, &rows));
+            WM_TRY(launch_nn_grid(ctx, ctx->shard_thr, e0, e1, nullptr, ctx->shard_params.mode, &rows));
         }
     }
     return launch_reduce_solve<1>(ctx, rows, static_cast<double *>(stats_dev));
@@ -2074,28 +2053,9 @@ int wm_debug_copy_bandwidth(wm_ctx *ctx, size_t bytes, int reps, double *gb_per_
 
 int wm_set_option(wm_ctx *ctx, const char *name, double value) {
     if (!ctx || !name) return WM_ERR_ARG;
-    const std::string k(name);
-    if (k == "cert_from") ctx->tune_cert_from = (int) value;
-    else if (k == "cert_nb") ctx->tune_cert_nb = (int) value;
-    else if (k == "cert_rc") ctx->tune_cert_rc = (int) value;
-    else if (k == "cert_disp" && value > 0) ctx->tune_cert_disp = (float) value;
-    else if (k == "cert_changed" && value > 0) ctx->tune_cert_changed = (float) value;
-    else if (k == "cert_unsettled" && value > 0) ctx->tune_cert_unsettled = (float) value;
-    else if (k == "cert_pad_mul" && value >= 0) ctx->tune_cert_pad_mul = (float) value;
-    else if (k == "cert_pad_frac" && value >= 0) ctx->tune_cert_pad_frac = (float) value;
-    else if (k == "late") ctx->tune_late = value != 0 ? 1 : 0;
-    else if (k == "bins") ctx->tune_bins = (int) value;
-    else if (k == "ndt_keys64") {
-        ctx->tune_ndt_keys64 = value != 0 ? 1 : 0;
-        ctx->ndt_built = false;
-    } else if (k == "ndt_vox_split") {  // developer: who forms a voxel's sums (wm_ndt.hip); the model is rebuilt
-        ctx->tune_ndt_vox_split = (int) value;
-        ctx->ndt_built = false;
-    }
-    else if (k == "gicp_served") ctx->tune_gicp_served = value == 2 ? 2 : (value != 0 ? 1 : 0);
-    else if (k == "gicp_serve_test_stall_ms") ctx->gicp_serve_test_stall_ms = (int) value;
-    else return WM_ERR_ARG;
-    return WM_OK;
+    for (const Option &o : kOptions)
+        if (strcmp(name, o.name) == 0) return apply_option(ctx, o, value);
+    return WM_ERR_ARG;
 }
 
 int wm_debug_cert_log(wm_ctx *ctx, int iterations, unsigned *out, int cap) {
@@ -2111,7 +2071,7 @@ int wm_debug_cert_log(wm_ctx *ctx, int iterations, unsigned *out, int cap) {
         }
         WM_HIP(ctx, ctx->cert_count.reserve((size_t) iterations * 64 * sizeof(unsigned)));
         WM_HIP(ctx, hipMemsetAsync(ctx->cert_count.p, 0, (size_t) iterations * 64 * sizeof(unsigned), ctx->stream));
-        if (getenv("WM_CERT_PROF")) {
+        if (ctx->cert_prof_on) {
             WM_HIP(ctx, ctx->cert_prof.reserve((size_t) iterations * 64 * sizeof(unsigned long long)));
             WM_HIP(ctx, hipMemsetAsync(ctx->cert_prof.p, 0, (size_t) iterations * 64 * sizeof(unsigned long long), ctx->stream));
         }

@@ -207,7 +207,7 @@ struct IcpDevState {
     double rot_thr, trans_thr, fit_eps;
     unsigned queue_count[kMaxLevels + 1];
     unsigned long long deferred_total;
-    int svd_warm;      // warm-started SVD on (tune_fast_solve)
+    int svd_warm;      // warm-started SVD on (always 1)
     double svd_v[10];  // V of the last iteration's SVD (+ a valid flag): the next one starts from it
     unsigned long long dbg[8];  // developer: cycle stamps of the last solve kernel (wm_debug_solve_cycles)
     unsigned cert_unsettled[64];  // k_nn_cert: queries it had to search in this iteration (partial counts; zeroed by the solve)
@@ -258,12 +258,55 @@ struct wm_ctx {
     int n_levels = 0;
     double levels_max_corr = -1;
     float grid_cell_override = 0;
-    bool trace = false;
+    // ---- options (wm_icp.hip: kOptions names each one for wm_set_option and for the environment)
+    int trace = 0;               // WM_TRACE: progress lines on stderr
+    // the grid search (wm_nn.hip)
     float tune_lane_lf = 0.2f;   // lane-serial scan: finest level with cell size >= this x radius
     float tune_coop_lf = 0.5f;   // cooperative scan: finest level with cell size >= this x radius
-    int tune_lag = 2;            // iterations the host may run ahead of the device (icp_run_loop)
     float tune_r0 = 0.5f;        // first radius of an unseeded search, in level-0 cells
     float tune_r_light = 16.0f;  // lane-serial vs cooperative scan threshold, in level-0 cells (12-24 within 1 %)
+    int tune_xcd_chunk = 32;     // search kernel: XCDs take turns in chunks of this many workgroups (0: one eighth each)
+    int tune_nn_balanced = 1;    // search kernel: wave-pooled candidate trips (0: every lane walks its own)
+    // the ICP loop
+    int tune_lag = 2;            // iterations the host may run ahead of the device (icp_run_loop), 1 ... 16
+    int tune_spin_us = 80;       // wait_flag: busy-poll this long before polling with yields
+    int tune_bins = 1;           // 0: rows of partial sums + k_reduce_rows + k_reduce_solve, as up to round 5
+    int tune_early_source = 2;   // a host target's upload overlaps the source's sort (wm_set_target); 2: and, from
+                                 // pinned memory, starts on a copy engine before that sort is enqueued
+    int tune_force_shard = 0;    // WM_SHARD_FORCE=1: a one-rank RCCL group still runs the sharded loop (plumbing check)
+    int tune_cert_from = -1;     // k_nn_cert from this iteration of an align on (-1: chosen from the step size, tune_cert_disp; -2: never)
+    float tune_cert_disp = 0.15f;  // ... once a step moves the points by less than this many level-0 cells
+    float tune_cert_changed = 0.05f;   // ... AND fewer than this fraction of the matches changed in the last full search
+    float tune_cert_unsettled = 0.40f; // back to full searches when a certificate launch had to search more than this fraction
+    float tune_cert_pad_mul = 8.f, tune_cert_pad_frac = 0.5f;  // runner-up room of a certified search (see k_nn_cert)
+    // 1: the late iterations run inside the resident kernel.  OFF by default: measured at 1M points
+    // (profiles/r04_experiments.md) an iteration inside costs 33-43 us against 32-37 us for a launched certificate
+    // iteration + its solve kernel -- the workers' certificate phase is bound by the vector ALU (~8 us chip-wide for the
+    // f64 sums of a million queries), the slowest workgroup's searches end 10 us after the median one's, and the
+    // solver's chain (rows 3.8, solve 4.4, hand-out 0.7 us) is serial behind them
+    int tune_late = 0;
+    // GICP (wm_gicp.hip)
+    int tune_gicp_served = 1;    // 0: a kernel launch per evaluation; 1: resident evaluator; 2: ... without the on-chip copy of the pairs
+    int gicp_serve_test_stall_ms = 0;  // test hook: the host sleeps this long before its third served evaluation
+    int tune_gicp_blocks = 256;  // workgroups (= partial rows) of one GICP objective evaluation (double-double sums: 512 / 256 / 128 / 64 -> 6.9 / 6.4 / 7.3 / 9.6 ms per 500k registration)
+    float tune_knn_r0 = 0.f;     // first radius of the k-NN (covariance) scan in cells, 0.25 ... 8; 0 = by k (1.0 up to k = 12, else 1.5)
+    int gicp_profile = 0;        // HIP events around every objective evaluation (fdf_kernel_ms)
+    // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
+    int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
+    int tune_ndt_dense = 2;      // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice
+    int tune_ndt_vox_split = -1; // developer: points per voxel up to which a LANE forms a voxel's sums (-1: ndt_build's choice)
+    int tune_ndt_keys64 = 0;     // developer: 64-bit voxel sort keys whatever the lattice's size
+    int tune_ndt_blocks = 0;     // workgroups (= partial rows) of one NDT derivative pass; 0: one resident round
+    int tune_ndt_spec_hessian = 1;  // form the Hessian along with the first extra line-search trial (step_length_mt)
+    int tune_ndt_fused_fetch = 1;   // a pass's last workgroup adds the rows and hands the sums to the host
+    int ndt_profile = 0;         // HIP events around every derivative pass (kernel_ms)
+    // developer instrumentation, armed by environment variables at wm_ctx_create only
+    int late_debug_iter = -1;    // WM_LATE_DEBUG: the resident kernel's stamps, its workers' of this iteration (-1: off)
+    bool cert_prof_on = false;   // WM_CERT_PROF: wm_debug_cert_log also arms the certificate kernel's phase stamps
+    std::string gicp_trace_path; // WM_GICP_TRACE: every GICP objective evaluation goes to this file
+    bool gicp_serve_debug = false;  // WM_GICP_SERVE_DEBUG: device-side stamps of the served evaluator's first rounds
+    int gicp_small_trace = 0;    // WM_GICP_SMALL_TRACE: the batched small GICP's trace (wm_gicp_small.hip)
+
     double tuned_h = 0, tuned_vol = 0;  // last auto-tuned level-0 cell size and its cloud
     size_t tuned_n = 0;
     double tuned_src_h = 0, tuned_src_vol = 0;  // the same for the source grid of the GICP covariances
@@ -284,8 +327,6 @@ struct wm_ctx {
     // zeros back)
     wm::DevBuf bins;
     bool bins_dirty = false;     // an iteration loop is running or ended abnormally: the bins may hold sums
-    int tune_grid_variant = 0;   // developer: k_nn_grid<SVD, balanced> at other register budgets (wm_nn.hip: launch_nn_grid)
-    int tune_bins = 1;           // 0: rows of partial sums + k_reduce_rows + k_reduce_solve, as up to round 5
     wm::DevBuf nn_bound;                    // float4 per (sorted) source point, written by k_nn_cert's searches: where the query was (xyz) and a lower bound (w) on its distance, there, to every target point but its match
     wm::DevBuf cert_count;                  // developer: unsettled queries per launch of k_nn_cert ([launch][64] partial counts)
     wm::DevBuf cert_prof;                   // developer: phase cycle sums per launch of k_nn_cert ([launch][8][8])
@@ -298,15 +339,6 @@ struct wm_ctx {
     unsigned late_seq = 0;
     int late_iters = 0, late_launches = 0;  // of the last align: iterations that ran inside it
     float late_ms = 0.f;                    // ... and its event-timed duration (profile >= 1)
-    // 1: use it.  OFF by default: measured at 1M points (profiles/r04_experiments.md) an iteration inside costs
-    // 33-43 us against 32-37 us for a launched certificate iteration + its solve kernel -- the workers' certificate
-    // phase is bound by the vector ALU (~8 us chip-wide for the f64 sums of a million queries), the slowest
-    // workgroup's searches end 10 us after the median one's, and the solver's chain (rows 3.8, solve 4.4, hand-out
-    // 0.7 us) is serial behind them
-    int tune_late = 0;
-    int tune_early_source = 2;              // a host target's upload overlaps the source's sort (wm_set_target); 2: and, from
-                                            // pinned memory, starts on a copy engine before that sort is enqueued
-    int tune_cov_dbg = 0;                   // developer timing experiment in k_gicp_cov (wrong results): see there
     unsigned long long *h_pub = nullptr;    // pinned: [0] (done << 63 | iterations finished << 32 | step size bits) of the latest solve, [k] iteration k's own record
     int h_pub_slots = 0;
     wm::DevBuf vg_idx, vg_idx2, vg_perm, vg_perm2, vg_tmp, vg_seg, io_a, io_b, ds_ref, ds_tgt, match_ref, match_tgt;
@@ -321,16 +353,12 @@ struct wm_ctx {
     unsigned gicp_serve_seq = 0;
     unsigned gicp_serve_abandoned = 0;      // rounds after which the evaluator's `abandoned` word was found set (diagnostic)
     int gicp_serve_ok = 0, gicp_serve_capacity = 0, gicp_serve_cached = 0;  // 0: not tried yet, 1: usable, -1: not on this system
-    int tune_gicp_served = 1;             // 0: a kernel launch per evaluation; 1: resident evaluator; 2: ... without the on-chip copy of the pairs
-    int gicp_serve_test_stall_ms = 0;     // test hook: the host sleeps this long before its third served evaluation
     void *h_gicp_slots = nullptr;         // pinned: the evaluator's answers, thirteen (sum, command number) pairs
     double *h_gicp = nullptr;            // pinned, device-visible: the GICP objective's partial sums land here
     int ndt_rank = 0, ndt_world = 1;     // wm_ndt_set_shard: this context's slice of the source
     int (*ndt_reduce)(double *, int, void *) = nullptr;
     void *ndt_reduce_user = nullptr;
     double *h_ndt = nullptr;             // pinned: the NDT derivative passes' block partials
-    bool ndt_profile = false;            // HIP events around every derivative pass (kernel_ms)
-    bool gicp_profile = false;           // HIP events around every objective evaluation (fdf_kernel_ms)
     bool have_corr = false, last_align_valid = false, last_align_converged = false;
     bool last_align_sharded = false;     // the last align was this rank's part of a sharded registration (wm_icp_info_sharded)
     wm::DevBuf keys_bak;
@@ -357,46 +385,15 @@ struct wm_ctx {
     wm::DevBuf ndt_keys, ndt_keys2, ndt_vox, ndt_vkey, ndt_hkeys, ndt_hvals, ndt_dense, ndt_meanf, ndt_vsum;
     bool ndt_dense_on = false;  // dense cell -> voxel-slot table built (small lattices)
     int ndt_dense_lo[3] = {0, 0, 0}, ndt_dense_dim[3] = {0, 0, 0};
-    int tune_ndt_keys64 = 0;      // developer: 64-bit voxel sort keys whatever the lattice's size (WM_TUNE_NDT_KEYS64)
-    int tune_ndt_vox_split = -1;  // developer: points per voxel up to which a LANE forms a voxel's sums (-1: ndt_build's choice)
-    int tune_ndt_dense = 2;  // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice (wm_ndt.hip)
     bool ndt_cells4_on = false;
     wm::DevBuf ndt_cells4;
-    float tune_knn_r0 = 0.f;     // first radius of the k-NN (covariance) scan in cells; 0 = by k (1.0 up to k = 12, else 1.5)
-    int tune_radix_min = 256 << 10;  // sorts of more items take the radix path (wm_sort.hpp) ...
-    int tune_pack_bbox = 1;          // a cloud's bounding box is formed by the launch that packs it (WM_TUNE_PACK_BBOX)
-    int tune_sort = 1;               // ... 1: the library's own three-launches-per-pass sort, 0: rocPRIM's onesweep (WM_TUNE_SORT)
-    int tune_xcd_chunk = 32;     // search kernel: XCDs take turns in chunks of this many workgroups (0: one eighth each)
-    int tune_scan = 1;           // exclusive scans: rocPRIM look-back scan (1) or the three-kernel scan (0)
-    int tune_nn_walk_filter = 1;  // balanced walk: LDS atomic only for trips that can improve the owner's best
-    int tune_xcd_reverse = 0;    // search kernel: hand the workgroups out back to front (experiment)
-    int tune_force_shard = 0;    // WM_SHARD_FORCE=1: a one-rank RCCL group still runs the sharded loop (plumbing check)
-    int tune_two_streams = 1;    // source Morton sort on a side stream beside the target's grid build
-    int tune_fuse_stats = 1;     // ICP statistics summed in the tail of the search kernel (0: separate k_icp_stats pass)
-    int tune_nn_balanced = 1;    // search kernel: wave-pooled candidate trips (0: every lane walks its own)
-    int tune_cert_from = -1;     // k_nn_cert from this iteration of an align on (-1: chosen from the step size, tune_cert_disp; -2: never)
-    float tune_cert_disp = 0.15f;  // ... once a step moves the points by less than this many level-0 cells
-    float tune_cert_changed = 0.05f;   // ... AND fewer than this fraction of the matches changed in the last full search
-    float tune_cert_unsettled = 0.40f; // back to full searches when a certificate launch had to search more than this fraction
-    float tune_cert_pad_mul = 8.f, tune_cert_pad_frac = 0.5f;  // runner-up room of a certified search (see k_nn_cert)
-    int tune_cert_nb = 4;        // batches of 64 queries per workgroup of k_nn_cert (2, 4 or 8)
-    int tune_cert_rc = 3;        // rows per step of its searches (3 or 6)
-    int tune_cert_dbg_skip = 0;  // developer timing experiment (wrong results): see k_nn_cert
-    int tune_nn_early_loads = 1; // k_nn_grid: the three stream loads issued before the state is looked at
-    int tune_nn_nt_stores = 1;   // search kernels: non-temporal result stores (nothing left dirty in L2 at the kernel boundary)
-    int tune_fast_solve = 1;     // experiment knob for the solve kernel
-    int tune_spin_us = 80;       // wait_flag: busy-poll this long before polling with yields
-    int tune_ndt_spec_hessian = 1;  // form the Hessian along with the first extra line-search trial (wm_ndt.hip step_length_mt)
-    int tune_ndt_blocks = 0;  // workgroups (= partial rows) of one NDT derivative pass; 0: one resident round (wm_ndt.hip)
     int ndt_cus = 0;
-    int tune_ndt_fused_fetch = 1;  // a pass's last workgroup adds the rows and hands the sums to the host (wm_ndt.hip)
     wm::DevBuf ndt_ticket;
     wm::DevBuf ndt_perm, ndt_perm2, ndt_flags, ndt_seg, ndt_tmp;  // ndt_build's scratch (its own: see there)
     bool xchg_timed_out = false;  // the last sharded loop ended because a peer's block did not arrive (wm_shard.hip)
     bool sort_join_pending = false;  // the source's Morton sort runs on the side stream, ev_join recorded, nobody waits yet
     bool sort_deferred = false;      // ... is still to be enqueued there (finalize_clouds mode 2: ev_fork recorded, n_src = the finite points' count)
     unsigned ndt_seq = 0;
-    int tune_gicp_blocks = 256;  // workgroups (= partial rows) of one GICP objective evaluation (double-double sums: 512 / 256 / 128 / 64 -> 6.9 / 6.4 / 7.3 / 9.6 ms per 500k registration)
     bool ndt_built = false;
     int ndt_model_builds = 0;    // voxel models built so far (wm_ndt_stats.model_builds)
     double ndt_res = -1;

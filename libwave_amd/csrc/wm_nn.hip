@@ -77,26 +77,15 @@ __device__ __forceinline__ float4 ldp(const float4 *p, size_t j) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ unsigned ldc(const unsigned *p, size_t j) { return ((gp_u32) p)[j]; }
-// Result stores.  `nt`: non-temporal -- the line does not stay (dirty) in the XCD's L2, so the kernel
+// Result stores are non-temporal: the line does not stay (dirty) in the XCD's L2, so the kernel
 // boundary behind the search has no write-back to wait for (a search leaves 12-26 MB of results that
 // nothing on this XCD reads again before the next iteration)
-__device__ __forceinline__ void st_f4(float4 *p, float x, float y, float z, float w, bool nt) {
+__device__ __forceinline__ void st_f4(float4 *p, float x, float y, float z, float w) {
     f4v v = {x, y, z, w};
-    if (nt) __builtin_nontemporal_store(v, (f4v *) p);
-    else *(f4v *) p = v;
+    __builtin_nontemporal_store(v, (f4v *) p);
 }
-__device__ __forceinline__ void st_u64(unsigned long long *p, unsigned long long v, bool nt) {
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-__device__ __forceinline__ void st_f32(float *p, float v, bool nt) {
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-__device__ __forceinline__ void st_f64(double *p, double v, bool nt) {
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+__device__ __forceinline__ void st_u64(unsigned long long *p, unsigned long long v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void st_f64(double *p, double v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ float canon_d2v(float qx, float qy, float qz, const f4v &t) {
     return canon_d2(qx, qy, qz, make_float4(t.x, t.y, t.z, t.w));
 }
@@ -445,7 +434,7 @@ __device__ __forceinline__ void balanced_walk(BalLds &L, const unsigned (&rs)[RC
                                               const unsigned (&re)[RC], unsigned lane,
                                               const float4 *pts, const float4 *ubase, float qx, float qy,
                                               float qz, unsigned long long &best, unsigned &cost,
-                                              unsigned long long *prof, bool filter, Bound *bnd = nullptr) {
+                                              unsigned long long *prof, Bound *bnd = nullptr) {
     const unsigned long long prof_t0 = COST ? clock64() : 0ull;
     unsigned len[RC], t = 0, longest = 0;
 #pragma unroll
@@ -494,7 +483,7 @@ __device__ __forceinline__ void balanced_walk(BalLds &L, const unsigned (&rs)[RC
         bnd->lds[lane] = bnd->second;
         reinterpret_cast<unsigned *>(&L.q[lane])[3] = __float_as_uint(pr * pr);
     } else {
-        reinterpret_cast<unsigned *>(&L.q[lane])[3] = filter ? (unsigned) (best >> 32) : 0x7F800000u;
+        reinterpret_cast<unsigned *>(&L.q[lane])[3] = (unsigned) (best >> 32);
     }
     __builtin_amdgcn_wave_barrier();  // (LDS operations of one wave execute in order; this only stops the compiler)
     pooled_rounds<BOUND>(L, L.items, T, lane, ubase, bnd);
@@ -514,8 +503,7 @@ __device__ __forceinline__ unsigned long long scan_box_bal(const GridDev &g, boo
                                                            float qz, float r, unsigned long long best,
                                                            float *margin, BalLds &L, unsigned lane,
                                                            bool allow_layered, const float4 *ubase,
-                                                           unsigned &cost, unsigned long long *prof, bool filter,
-                                                           Bound *bnd = nullptr) {
+                                                           unsigned &cost, unsigned long long *prof, Bound *bnd = nullptr) {
     const float big = 4.0e6f;
     const float fx = fminf(fmaxf((qx - g.ox) * g.inv_h, -big), big);
     const float fy = fminf(fmaxf((qy - g.oy) * g.inv_h, -big), big);
@@ -540,7 +528,7 @@ __device__ __forceinline__ unsigned long long scan_box_bal(const GridDev &g, boo
             re[u] = ldc(g.cell_start, a1[u]);
         }
         if constexpr (COST) cost += has ? 1u << 16 : 0u;
-        balanced_walk<COST, RC, BOUND>(L, rs, re, lane, g.pts, ubase, qx, qy, qz, best, cost, prof, filter, bnd);
+        balanced_walk<COST, RC, BOUND>(L, rs, re, lane, g.pts, ubase, qx, qy, qz, best, cost, prof, bnd);
     };
     // radius (cell units) beyond which a point cannot matter: the best distance so far -- or, with
     // runner-up tracking, the prune radius
@@ -903,12 +891,12 @@ __device__ __forceinline__ void icp_terms(double (&a)[kAcc], bool mine, bool mat
 // WM_ICP_GN6: the wave also reduces the ICP statistics of its 64 queries to ONE row of `partials`
 // ([gridDim.x][kAcc]).  BAL: the wave pools its lanes' candidate trips (balanced walk, above);
 // otherwise every lane walks its own (kept for targets of 2^26 points and more, and for comparison).
-template <int STATS, bool BAL, bool COST = false, int RC = kBalRowChunk, int WPE = 5>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
+template <int STATS, bool BAL, bool COST = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
     k_nn_grid(const LevelsDev *__restrict__ lv, const float4 *__restrict__ src, unsigned n,
               IcpDevState *__restrict__ st, float thr_d2, unsigned long long *__restrict__ keys,
               float4 *__restrict__ match_pt, const float4 *__restrict__ tgt_orig,
-              float r_light_cells, float lane_lf, float coop_lf, float r0_cells, unsigned xcd_chunk,
+              float r_light_cells, float lane_lf, float coop_lf, float r0_cells, unsigned chunk_sz,
               double *__restrict__ partials, unsigned *__restrict__ cost_out,
               unsigned long long *__restrict__ phase_out, long long *__restrict__ bins) {
     // (bins != nullptr: the wave's sums are ADDED into the iteration's bins -- exact integer limbs, any order:
@@ -917,24 +905,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     // point, previous key, previous match -- need nothing but the block number for their addresses
     // and are requested before the state is looked at.  Before the first search keys / match_pt hold
     // nothing meaningful and are not looked at.)
-    const bool early = ((xcd_chunk >> 29) & 1u) != 0u;
-    const bool rev = (xcd_chunk >> 31) != 0u;  // experiment: hand the queries out back to front
-    const unsigned chunk_sz = xcd_chunk & 0x0FFFFFFFu;
-    const bool nt = ((xcd_chunk >> 28) & 1u) != 0u;  // non-temporal result stores
-    const bool walk_filter = ((xcd_chunk >> 30) & 1u) != 0u;  // see balanced_walk
-    const unsigned bidx = rev ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
+    // (chunk_sz: the XCDs take turns in chunks of this many workgroups, 0: one eighth of the queries each)
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned row = chunk_sz ? xcd_remap_chunked(bidx, chunk_sz) : xcd_remap(bidx, gridDim.x);
+    const unsigned row = chunk_sz ? xcd_remap_chunked(blockIdx.x, chunk_sz) : xcd_remap(blockIdx.x, gridDim.x);
     const unsigned i = row * 64u + lane;
     const bool active = i < n;
-    float4 p_e = make_float4(0.f, 0.f, 0.f, 0.f), tp_e = p_e;
-    unsigned long long prev_e = ~0ull;
-    if (early) {
-        const unsigned ic = min(i, n - 1u);
-        p_e = src[ic];
-        prev_e = keys[ic];
-        tp_e = match_pt[ic];
-    }
+    const unsigned ic = min(i, n - 1u);
+    const float4 p_e = src[ic];
+    const unsigned long long prev_e = keys[ic];
+    const float4 tp_e = match_pt[ic];
     if (st->done) return;
     unsigned cost = 0;
     // developer (COST): shader-clock cycles of this wave's phases, added into phase_out[8] by lane 0:
@@ -960,18 +939,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     unsigned long long seeded = best;  // the key the search started from
     bool heavy = false;
     bool mine = active;
-    // the query and its seed (previous key + previous match coordinates) are three
-    // independent streams: all three loads are issued before the first use -- one memory round
-    // trip, not three dependent ones
     unsigned long long prev = ~0ull;
     float4 tp = make_float4(0.f, 0.f, 0.f, 0.f);
     if (active) {
-        const float4 p = early ? p_e : src[i];
         if (have_prev) {
-            prev = early ? prev_e : keys[i];
-            tp = early ? tp_e : match_pt[i];
+            prev = prev_e;
+            tp = tp_e;
         }
-        xform(st->Tf, p, qx, qy, qz);
+        xform(st->Tf, p_e, qx, qy, qz);
         // sharded registration: only the rank owning this x-slab handles the point
         if (st->slab_on && !(qx >= st->slab_lo && qx < st->slab_hi)) mine = false;
     }
@@ -1023,11 +998,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
             float margin;
             if (__ballot(live && l != l0) == 0ull) {
                 const GridDev g = lv->g[l0];
-                best = scan_box_bal<COST, RC>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev, g.pts, cost, prof, walk_filter);
+                best = scan_box_bal<COST, kBalRowChunk>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev, g.pts, cost, prof);
             } else {
                 const GridDev g = lv->g[l];
                 L.base[lane] = (unsigned long long) g.pts;
-                best = scan_box_bal<COST, RC>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev, nullptr, cost, prof, walk_filter);
+                best = scan_box_bal<COST, kBalRowChunk>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev, nullptr, cost, prof);
             }
             if (live) {
                 if constexpr (COST) cost += 1u << 24;
@@ -1101,7 +1076,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         bqz = L.bq[2][lane_e];
     }
     if (mine) {
-        st_u64(&keys[i_e], best, nt);
+        st_u64(&keys[i_e], best);
         // the match's coordinates ride along for the statistics kernel and for the next
         // iteration's seed; a new winner's are read from the caller-ordered target copy
         // (its key carries the original index)
@@ -1115,7 +1090,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         // itself under this pose, is still the best -- finds match_pt[i] already holding these very coordinates and
         // this index: no store (16 of the 24 result bytes of most queries once the clouds are close)
         if (!(best == seeded && (unsigned) best != kNoIdx))
-            st_f4(&match_pt[i_e], bqx, bqy, bqz, __uint_as_float((unsigned) best), nt);
+            st_f4(&match_pt[i_e], bqx, bqy, bqz, __uint_as_float((unsigned) best));
     }
     if (lane == 0 && n_heavy) atomicAdd(&st->queue_count[1], n_heavy);  // stats only
     const unsigned long long prof_store = COST ? clock64() : 0ull;
@@ -1131,7 +1106,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         const int comp = acc_comp_of_lane(lane);
         if (comp >= 0) {
             if (bins) bins_add(bins, row % (unsigned) kBinCount, (unsigned) comp, a[0]);
-            else st_f64(&partials[(size_t) row * kAcc + comp], a[0], nt);
+            else st_f64(&partials[(size_t) row * kAcc + comp], a[0]);
         }
     }
     if constexpr (COST) {
@@ -1356,14 +1331,12 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// (P1: developer timing experiment, WRONG results -- phase 2 compiled OUT: what the certificate phase costs in a kernel
-// whose registers, scalar registers and LDS are not set by the searches; launched for bounds-valid launches only)
-template <int STATS, int NB, int RC, bool LATE = false, bool P1 = false>
-__global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_per_eu(P1 ? 6 : 4, P1 ? 6 : 4)))
+template <int STATS, int NB, int RC, bool LATE = false>
+__global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_per_eu(4, 4)))
     k_nn_cert(const LevelsDev *__restrict__ lv, const float4 *__restrict__ src, unsigned n,
               IcpDevState *__restrict__ st, float thr_d2, unsigned long long *__restrict__ keys,
               float4 *__restrict__ match_pt, float4 *__restrict__ bound, const float4 *__restrict__ tgt_orig,
-              float r_light_cells, float lane_lf, float coop_lf, float r0_cells, unsigned xflags,
+              float r_light_cells, float lane_lf, float coop_lf, float r0_cells,
               double *__restrict__ partials, int bounds_valid, float pad_mul, float pad_frac,
               unsigned *__restrict__ uns_count, unsigned long long *__restrict__ prof_out, LateArgs la,
               long long *__restrict__ bins) {
@@ -1373,8 +1346,6 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
     // anything else is looked at -- their addresses need nothing but the block number)
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    const bool nt = ((xflags >> 28) & 1u) != 0u;  // non-temporal result stores (st_f4 ...)
-    const unsigned dbg_skip = (xflags >> 26) & 3u;  // developer timing experiment (WRONG results): 1 = no phase 2, 2 = phase 2 without its scans
     const unsigned row = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned gbase = row * (64u * NB * kCertWaves);  // the workgroup's first query
     const unsigned base = gbase + wave * (64u * NB);        // the wave's
@@ -1413,7 +1384,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
         if (st->done) return;  // (a launch queued behind a `done`; the solver tells the host)
     }
     BalLds &L = s_L[wave];
-    if constexpr (!P1) s_win[wave][lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kNoIdx));  // (no winner recorded)
+    s_win[wave][lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kNoIdx));  // (no winner recorded)
     const int Ln = lv->n;
     float hl[kMaxLevels];  // the levels' cell sizes (wave-uniform: scalar registers)
 #pragma unroll
@@ -1596,7 +1567,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
             }
             const bool uns = owned && !settled;
             const unsigned long long umask = __ballot(uns);
-            if (!P1 && uns) {
+            if (uns) {
                 const unsigned before = __builtin_amdgcn_mbcnt_hi((unsigned) (umask >> 32),
                                                                   __builtin_amdgcn_mbcnt_lo((unsigned) umask, 0u));
                 const unsigned e = n_uns + before;
@@ -1621,22 +1592,19 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
     cum[0] = 0;
 #pragma unroll
     for (int w = 0; w < kCertWaves; ++w) cum[w + 1] = cum[w] + s_cnt[w];
-    unsigned U = cum[kCertWaves];
+    const unsigned U = cum[kCertWaves];
     if (uns_count && threadIdx.x == 0 && U) atomicAdd(&uns_count[blockIdx.x & 63u], U);  // developer statistics
     // how many queries this launch had to search: the solve kernel hands it to the host (one atomic per
     // workgroup, spread over 64 words)
     // (with bins the count is one of their components)
     if (!LATE && !bins && threadIdx.x == 0 && U) atomicAdd(&st->cert_unsettled[blockIdx.x & 63u], U);
-    const unsigned U_searched = U;
-    if (dbg_skip == 1u && valid) U = 0;
-    if constexpr (P1) U = 0;
     const unsigned nchunks = (U + 63u) / 64u;
     unsigned cost = 0;
     unsigned long long prof[3] = {0ull, 0ull, 0ull};
     // The wave's first chunk is gathered from the four waves' parked entries BEFORE any wave scans (a
     // scan overwrites its wave's parking area), and set down again in the wave's own area after the
     // barrier: query (pose applied), its index, its match.
-    if constexpr (!P1) {
+    {
         float gx = 0.f, gy = 0.f, gz = 0.f;
         float4 gtp = make_float4(0.f, 0.f, 0.f, __uint_as_float(kNoIdx));
         unsigned gi = kNoIdx;
@@ -1734,7 +1702,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
         L.bq[1][lane] = bqy;
         L.bq[2][lane] = bqz;
         asm volatile("" ::: "memory");
-        bool live = mine && !heavy && !(dbg_skip == 2u && valid);
+        bool live = mine && !heavy;
         for (int pass = 0; pass < 32 && __ballot(live) != 0ull; ++pass) {
             int l = 0;  // the finest level whose cell is >= lane_lf * r (cell sizes double from level to level)
 #pragma unroll
@@ -1746,12 +1714,12 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 const GridDev g = l0 == 0 ? g0 : lv->g[l0];
                 if (!scan_box_rows(g, live, qx, qy, qz, r, best, &margin, L, lane, &bnd))
                     best = scan_box_bal<false, RC, true>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev,
-                                                          g.pts, cost, prof, true, &bnd);
+                                                          g.pts, cost, prof, &bnd);
             } else {
                 const GridDev g = lv->g[l];
                 L.base[lane] = (unsigned long long) g.pts;
                 best = scan_box_bal<false, RC, true>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev,
-                                                      nullptr, cost, prof, true, &bnd);
+                                                      nullptr, cost, prof, &bnd);
             }
             if (live) {
                 const float bd2 = __uint_as_float((unsigned) (best >> 32));
@@ -1812,7 +1780,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
         bqz = L.bq[2][lane];
         if (c == wave) WM_STAMP(6);  // first chunk: cooperative phase done
         if (mine) {
-            st_u64(&keys[i], best, nt);
+            st_u64(&keys[i], best);
             if (best != seeded && (unsigned) best != kNoIdx) {
                 // the new match's coordinates: left in LDS by the lane that found it (the tag says whether
                 // the slot really is this point's), else from the caller-ordered target copy
@@ -1828,7 +1796,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                     bqz = cc.z;
                 }
             }
-            st_f4(&match_pt[i], bqx, bqy, bqz, __uint_as_float((unsigned) best), nt);
+            st_f4(&match_pt[i], bqx, bqy, bqz, __uint_as_float((unsigned) best));
             // every point but the match is farther than: the runner-up seen, the radius pruned with, and
             // the faces of the last box scanned
             float s = 0.f;
@@ -1836,7 +1804,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 const float bd = sqrtf(__uint_as_float((unsigned) (best >> 32)));
                 s = fminf(fminf(sqrtf(__uint_as_float(bnd.second)), bd + pad), margin_last) * 0.9999f - 1e-6f;
             }
-            st_f4(&bound[i], qx, qy, qz, s, nt);  // ... seen from HERE
+            st_f4(&bound[i], qx, qy, qz, s);  // ... seen from HERE
         }
         if (c == wave) WM_STAMP(7);  // first chunk: winners fetched, results stored
         if constexpr (STATS >= 0) {
@@ -1860,7 +1828,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         WM_WSTAMP(3);  // all waves' searches done, result stores performed
-        if (threadIdx.x == 0 && la.dbg_w && li == la.dbg_li) la.dbg_w[(size_t) blockIdx.x * 8u + 6u] = U_searched;
+        if (threadIdx.x == 0 && la.dbg_w && li == la.dbg_li) la.dbg_w[(size_t) blockIdx.x * 8u + 6u] = U;
         if (threadIdx.x < (unsigned) kAcc + 1u) {
             double t;
             if (threadIdx.x < (unsigned) kAcc) {
@@ -1868,7 +1836,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
 #pragma unroll
                 for (int w = 1; w < kCertWaves; ++w) t += s_rows[w][threadIdx.x];
             } else {
-                t = (double) U_searched;
+                t = (double) U;
             }
             __hip_atomic_store(partials + (size_t) row * kLateRow + threadIdx.x, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1887,14 +1855,14 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
 #pragma unroll
                 for (int w = 1; w < kCertWaves; ++w) t += s_rows[w][threadIdx.x];
                 bins_add(bins, row % (unsigned) kBinCount, threadIdx.x, t);
-            } else if (threadIdx.x == (unsigned) kAcc && U_searched) {
-                bins_add_count(bins, row % (unsigned) kBinCount, (unsigned) kAcc, (long long) U_searched);
+            } else if (threadIdx.x == (unsigned) kAcc && U) {
+                bins_add_count(bins, row % (unsigned) kBinCount, (unsigned) kAcc, (long long) U);
             }
         } else if (threadIdx.x < (unsigned) kAcc) {
             double t = s_rows[0][threadIdx.x];
 #pragma unroll
             for (int w = 1; w < kCertWaves; ++w) t += s_rows[w][threadIdx.x];
-            st_f64(&partials[(size_t) row * kAcc + threadIdx.x], t, nt);
+            st_f64(&partials[(size_t) row * kAcc + threadIdx.x], t);
         }
     }
     if (stamp_on && lane == 0) {
@@ -2008,9 +1976,9 @@ float threshold_d2_strict(double max_corr) {
     return f;
 }
 
-template <int STATS, bool BAL, bool COST = false, int RC = kBalRowChunk, int WPE = 5>
+template <int STATS, bool BAL, bool COST = false>
 static void launch_nn_grid_t(wm_ctx *ctx, unsigned blocks, float thr_d2, unsigned xcd_chunk, long long *bins = nullptr) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_grid<STATS, BAL, COST, RC, WPE>), dim3(blocks), dim3(64), 0, ctx->stream,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_grid<STATS, BAL, COST>), dim3(blocks), dim3(64), 0, ctx->stream,
                        ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
                        ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),
                        ctx->match_pt.as<float4>(), ctx->tgt_orig.as<float4>(), ctx->tune_r_light,
@@ -2045,10 +2013,6 @@ int launch_nn_grid(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hi
         WM_HIP(ctx, ctx->partials.reserve((size_t) blocks * kAcc * sizeof(double)));
         if (rows_out) *rows_out = blocks;
     }
-    xcd_chunk |= ctx->tune_xcd_reverse ? 0x80000000u : 0u;
-    xcd_chunk |= ctx->tune_nn_walk_filter ? 0x40000000u : 0u;
-    xcd_chunk |= ctx->tune_nn_early_loads ? 0x20000000u : 0u;
-    xcd_chunk |= ctx->tune_nn_nt_stores ? 0x10000000u : 0u;
     // the balanced walk packs (lane, point offset) into 32 bits: targets below 2^26 points
     const bool bal = ctx->tune_nn_balanced && ctx->n_tgt_input < (1u << 26) - 8u;
     if (ev0) WM_HIP(ctx, hipEventRecord(ev0, ctx->stream));
@@ -2060,12 +2024,7 @@ int launch_nn_grid(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hi
         if (bal) launch_nn_grid_t<-1, true>(ctx, blocks, thr_d2, xcd_chunk);
         else launch_nn_grid_t<-1, false>(ctx, blocks, thr_d2, xcd_chunk);
     } else if (stats_mode == WM_ICP_SVD) {
-        // (developer: registers per wave of the production instantiation -- waves per SIMD 4 / 6 and rows per step 2)
-        if (bal && ctx->tune_grid_variant == 1) launch_nn_grid_t<WM_ICP_SVD, true, false, 3, 4>(ctx, blocks, thr_d2, xcd_chunk, bins);
-        else if (bal && ctx->tune_grid_variant == 2) launch_nn_grid_t<WM_ICP_SVD, true, false, 3, 6>(ctx, blocks, thr_d2, xcd_chunk, bins);
-        else if (bal && ctx->tune_grid_variant == 3) launch_nn_grid_t<WM_ICP_SVD, true, false, 2, 5>(ctx, blocks, thr_d2, xcd_chunk, bins);
-        else if (bal && ctx->tune_grid_variant == 4) launch_nn_grid_t<WM_ICP_SVD, true, false, 2, 6>(ctx, blocks, thr_d2, xcd_chunk, bins);
-        else if (bal) launch_nn_grid_t<WM_ICP_SVD, true>(ctx, blocks, thr_d2, xcd_chunk, bins);
+        if (bal) launch_nn_grid_t<WM_ICP_SVD, true>(ctx, blocks, thr_d2, xcd_chunk, bins);
         else launch_nn_grid_t<WM_ICP_SVD, false>(ctx, blocks, thr_d2, xcd_chunk, bins);
     } else {
         if (bal) launch_nn_grid_t<WM_ICP_GN6, true>(ctx, blocks, thr_d2, xcd_chunk, bins);
@@ -2077,13 +2036,14 @@ int launch_nn_grid(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hi
     return WM_OK;
 }
 
-template <int STATS, int NB, int RC>
-static void launch_nn_cert_t(wm_ctx *ctx, unsigned blocks, float thr_d2, unsigned xcd_chunk, bool bounds_valid, long long *bins) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_cert<STATS, NB, RC, false>), dim3(blocks), dim3(64 * kCertWaves), 0, ctx->stream,
+constexpr int kCertNB = 4;  // batches of 64 queries per workgroup of k_nn_cert
+template <int STATS>
+static void launch_nn_cert_t(wm_ctx *ctx, unsigned blocks, float thr_d2, bool bounds_valid, long long *bins) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_cert<STATS, kCertNB, 3, false>), dim3(blocks), dim3(64 * kCertWaves), 0, ctx->stream,
                        ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
                        ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),
                        ctx->match_pt.as<float4>(), ctx->nn_bound.as<float4>(), ctx->tgt_orig.as<float4>(),
-                       ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0, xcd_chunk,
+                       ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0,
                        ctx->partials.as<double>(), bounds_valid ? 1 : 0, ctx->tune_cert_pad_mul,
                        ctx->tune_cert_pad_frac,
                        ctx->cert_count.p && ctx->cert_log_iter < ctx->cert_log_cap
@@ -2093,14 +2053,6 @@ static void launch_nn_cert_t(wm_ctx *ctx, unsigned blocks, float thr_d2, unsigne
                        LateArgs{}, bins);
 }
 
-template <int NB, int RC>
-static void launch_nn_cert_nb(wm_ctx *ctx, unsigned blocks, float thr_d2, unsigned xcd_chunk, bool bounds_valid,
-                              int stats_mode, long long *bins) {
-    if (stats_mode < 0) launch_nn_cert_t<-1, NB, RC>(ctx, blocks, thr_d2, xcd_chunk, bounds_valid, nullptr);
-    else if (stats_mode == WM_ICP_SVD) launch_nn_cert_t<WM_ICP_SVD, NB, RC>(ctx, blocks, thr_d2, xcd_chunk, bounds_valid, bins);
-    else launch_nn_cert_t<WM_ICP_GN6, NB, RC>(ctx, blocks, thr_d2, xcd_chunk, bounds_valid, bins);
-}
-
 // use_bins (with a stats_mode): sums and the searched-queries count go into the iteration's bins (wm_bins.hpp) --
 // *rows_out is 0 then, and the solve is launch_bins_solve
 int launch_nn_cert(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, int stats_mode,
@@ -2108,8 +2060,7 @@ int launch_nn_cert(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hi
     const unsigned n = (unsigned) ctx->n_src;
     if (rows_out) *rows_out = 0;
     if (n == 0) return WM_OK;
-    const int nb = ctx->tune_cert_nb == 2 ? 2 : 4;
-    const unsigned per = 64u * (unsigned) nb * (unsigned) kCertWaves;
+    const unsigned per = 64u * (unsigned) kCertNB * (unsigned) kCertWaves;
     unsigned blocks = (n + per - 1u) / per;
     blocks = (blocks + 7u) & ~7u;  // xcd_remap needs a multiple of 8
     WM_HIP(ctx, ctx->nn_bound.reserve(((size_t) n + 64) * sizeof(float4)));
@@ -2121,18 +2072,10 @@ int launch_nn_cert(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hi
         WM_HIP(ctx, ctx->partials.reserve((size_t) blocks * kAcc * sizeof(double)));
         if (rows_out) *rows_out = blocks;
     }
-    const unsigned xflags = (ctx->tune_nn_nt_stores ? 0x10000000u : 0u) | (((unsigned) ctx->tune_cert_dbg_skip & 3u) << 26);
     if (ev0) WM_HIP(ctx, hipEventRecord(ev0, ctx->stream));
-    if (ctx->tune_cert_dbg_skip == 3 && bounds_valid && stats_mode == WM_ICP_SVD && nb == 4) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_cert<WM_ICP_SVD, 4, 3, false, true>), dim3(blocks), dim3(64 * kCertWaves), 0, ctx->stream,
-                           ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
-                           ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),
-                           ctx->match_pt.as<float4>(), ctx->nn_bound.as<float4>(), ctx->tgt_orig.as<float4>(),
-                           ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0, xflags,
-                           ctx->partials.as<double>(), 1, ctx->tune_cert_pad_mul, ctx->tune_cert_pad_frac,
-                           (unsigned *) nullptr, (unsigned long long *) nullptr, LateArgs{}, bins);
-    } else if (nb == 2) launch_nn_cert_nb<2, 3>(ctx, blocks, thr_d2, xflags, bounds_valid, stats_mode, bins);
-    else launch_nn_cert_nb<4, 3>(ctx, blocks, thr_d2, xflags, bounds_valid, stats_mode, bins);
+    if (stats_mode < 0) launch_nn_cert_t<-1>(ctx, blocks, thr_d2, bounds_valid, nullptr);
+    else if (stats_mode == WM_ICP_SVD) launch_nn_cert_t<WM_ICP_SVD>(ctx, blocks, thr_d2, bounds_valid, bins);
+    else launch_nn_cert_t<WM_ICP_GN6>(ctx, blocks, thr_d2, bounds_valid, bins);
     if (ctx->cert_count.p && ctx->cert_log_iter < ctx->cert_log_cap) ctx->cert_log_iter++;
     if (ev1) WM_HIP(ctx, hipEventRecord(ev1, ctx->stream));
     if (ev2) WM_HIP(ctx, hipEventRecord(ev2, ctx->stream));
@@ -2215,16 +2158,15 @@ int launch_nn_late(wm_ctx *ctx, float thr_d2, int stats_mode, unsigned blocks, b
     la.stop_unsettled = stop_unsettled;
     la.stop_disp = stop_disp;
     la.max_inside = max_inside;
-    la.dbg = getenv("WM_LATE_DEBUG") ? (unsigned long long *) ((char *) ctx->late_ctl.p + sizeof(LateCtl)) : nullptr;
+    la.dbg = ctx->late_debug_iter >= 0 ? (unsigned long long *) ((char *) ctx->late_ctl.p + sizeof(LateCtl)) : nullptr;
     la.dbg_w = nullptr;
     la.dbg_li = 0;
     if (la.dbg) {
         WM_HIP(ctx, ctx->cert_prof.reserve((size_t) workers * 8 * sizeof(unsigned long long)));
         WM_HIP(ctx, hipMemsetAsync(ctx->cert_prof.p, 0, (size_t) workers * 8 * sizeof(unsigned long long), ctx->stream));
         la.dbg_w = ctx->cert_prof.as<unsigned long long>();
-        la.dbg_li = (unsigned) atoi(getenv("WM_LATE_DEBUG"));
+        la.dbg_li = (unsigned) ctx->late_debug_iter;
     }
-    const unsigned xflags = (ctx->tune_nn_nt_stores ? 0x10000000u : 0u);
     // the solver beside the workers, on the second stream: both start when what is on the main stream now is done
     WM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     WM_HIP(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
@@ -2237,7 +2179,7 @@ int launch_nn_late(wm_ctx *ctx, float thr_d2, int stats_mode, unsigned blocks, b
                        ctx->stream, ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), n,                       \
                        ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),                        \
                        ctx->match_pt.as<float4>(), ctx->nn_bound.as<float4>(), ctx->tgt_orig.as<float4>(),                \
-                       ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0, xflags,                     \
+                       ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0,                             \
                        ctx->partials.as<double>(), bounds_valid ? 1 : 0, ctx->tune_cert_pad_mul, ctx->tune_cert_pad_frac, \
                        (unsigned *) nullptr, (unsigned long long *) nullptr, la, (long long *) nullptr)
     if (stats_mode == WM_ICP_SVD) WM_LATE_LAUNCH(WM_ICP_SVD);

@@ -922,7 +922,7 @@ int small_run(wm_ctx *ctx, const SmallJob *jobs, int n, size_t stride, int mem, 
     st0.rot_thr = 1.0 - p->t_eps;
     st0.trans_thr = p->t_eps;
     st0.fit_eps = p->fit_eps;
-    st0.svd_warm = ctx->tune_fast_solve ? 1 : 0;
+    st0.svd_warm = 1;
     SmallParams P;
     memset(&P, 0, sizeof(P));
     P.stride = (unsigned) stride;

@@ -11,10 +11,9 @@
 //   rocPRIM's 101 / 107 / 118 -- whose onesweep path is a histogram kernel, a scan, and per pass two memsets of its
 //   look-back state and a 26-33 us pass: twelve dependent launches whose floor is their number, not their bytes (nine
 //   here; per pass at 1M: histogram 6.5, scan 4.8, scatter 13.8 us).
-// * rocPRIM (small clouds: its merge sort; WM_TUNE_SORT=0: its onesweep radix sort as before).
-//   rocPRIM's default dispatch takes its MERGE sort for up to 1 M items (log2(n / 4096) merge passes of two kernels each,
-//   whatever the key width); the keys here are narrow (17-30 bits: leaf / Morton indices), so above `radix_min` items
-//   (256 k by default) the radix path is selected explicitly (merge-sort limit 0).
+// * rocPRIM (small clouds).  Its default dispatch takes its MERGE sort for up to 1 M items (log2(n / 4096) merge passes
+//   of two kernels each, whatever the key width); the keys here are narrow (17-30 bits: leaf / Morton indices), so above
+//   `radix_min` items (256 k by default) the sort above takes over.
 #ifndef WM_SORT_HPP
 #define WM_SORT_HPP
 
@@ -225,23 +224,17 @@ inline hipError_t rs_sort_pairs(void *tmp, K *keys_in, K *keys_out, V *vals_in, 
     return hipGetLastError();
 }
 
-// own: 1 = rs_sort_pairs above radix_min items (the default), 0 = rocPRIM throughout
 template <class K, class V>
 inline hipError_t sort_pairs_low_bits(void *tmp, size_t &tmp_bytes, K *keys_in, K *keys_out, V *vals_in,
                                       V *vals_out, size_t n, unsigned bits, hipStream_t stream,
-                                      size_t radix_min = (size_t) (256u << 10), int own = 1) {
-    using radix_only = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                  rocprim::default_config, 0>;
-    if (n > radix_min && own && n < (size_t) 0xFFFF0000u) {
+                                      size_t radix_min = (size_t) (256u << 10)) {
+    if (n > radix_min && n < (size_t) 0xFFFF0000u) {
         if (tmp == nullptr) {
             tmp_bytes = rs_temp_bytes(n);
             return hipSuccess;
         }
         return rs_sort_pairs(tmp, keys_in, keys_out, vals_in, vals_out, n, bits, stream);
     }
-    if (n > radix_min)
-        return rocprim::radix_sort_pairs<radix_only>(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, n,
-                                                     0u, bits, stream);
     return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, bits, stream);
 }
 

@@ -6,7 +6,6 @@ import numpy as np, torch
 from libwave_amd import capi, synth
 ref, tgt, T_gt = synth.pair(2_000_000, seed=42, pattern="rings")
 d_ref, d_tgt = torch.from_numpy(ref).cuda(), torch.from_numpy(tgt).cuda()
-os.environ["WM_TUNE_NDT_GROUP"] = "0"
 os.environ["WM_NDT_PROFILE"] = "1"
 c = capi.Context(0)
 c.set_source(d_ref); c.set_target(d_tgt)
