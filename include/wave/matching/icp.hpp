@@ -77,6 +77,18 @@ class ICPMatcher : public Matcher<PCLPointCloudPtr> {
     // WAVE_ICP_BENCH_FORCE_ITERATIONS does the same.
     static void setBenchForceIterations(int n);
 
+    // The residual an iteration minimises (no reference counterpart: libwave's ICPMatcher is point-to-point only).
+    // PointToPoint (the default): PCL's Umeyama step on |p - q|.  PointToPlane: n . (p - q) with normals of the target
+    // estimated on the device from each point's setNormalK() nearest neighbours (3 ... 32; 0 = the default, 20) --
+    // pcl::IterativeClosestPointWithNormals; the stopping rules are the same.  Fewer iterations on scans of surfaces; a
+    // scene that leaves a motion free (a single plane) makes match() return false.  A matcher that was never told
+    // takes env WAVE_ICP_ERROR_METRIC=plane, else PointToPoint.  Not available with setDevices() of several devices
+    // (match() returns false); MultiMatcher queues register such pairs one after the other inside the batch call.
+    enum class ErrorMetric { PointToPoint, PointToPlane };
+    void setErrorMetric(ErrorMetric m);
+    ErrorMetric getErrorMetric() const;
+    void setNormalK(int k);
+
     // Spread ONE registration over several GPUs of the node (no reference counterpart): the target is
     // cut into equal-count x-slabs, one per device, every device searches the source points that fall
     // into its slab, and the per-iteration statistics are summed by an RCCL all-reduce over xGMI inside
@@ -124,6 +136,8 @@ class ICPMatcher : public Matcher<PCLPointCloudPtr> {
     // (ctx) or over the group (multi); neither after a failed match, a matchBatch() or a change of devices
     enum { kNone, kOnCtx, kOnMulti } lastMatch;
     PCLPointCloudPtr ref, target;
+    int errorMetric = -1;  // WM_ICP_SVD / WM_ICP_PLANE; -1: not told (the environment decides)
+    int normalK = 0;
 
     bool ensureContext();
     void estimateLUM();

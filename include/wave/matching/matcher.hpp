@@ -10,7 +10,9 @@
 //   * no initial guess: matchers start from identity; pre-transform `target` if you have one;
 //   * getResult() maps `ref` onto `target` (the reference's tests are the authority:
 //     tests/icp_tests.cpp:31-32,59);
-//   * information is ordered (x, y, z, then the three Euler angles) in the frame of `ref`.
+//   * information is ordered (x, y, z, then the three Euler angles) in the frame of `ref`;
+//   * ICPMatcher minimises point-to-point distances, as the reference; point-to-plane is an opt-in
+//     (ICPMatcher::setErrorMetric), with normals of `target` turned towards the origin of its frame (the sensor).
 #ifndef WAVE_MATCHING_MATCHER_HPP
 #define WAVE_MATCHING_MATCHER_HPP
 

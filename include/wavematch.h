@@ -83,7 +83,10 @@ int wm_set_grid_cell(wm_ctx *ctx, float grid_cell);
 int wm_cloud_sizes(const wm_ctx *ctx, size_t *n_source, size_t *n_target);
 
 /* ------------------------------------------------------------------- ICP */
-enum { WM_ICP_SVD = 0, WM_ICP_GN6 = 1 };
+enum { WM_ICP_SVD = 0, WM_ICP_GN6 = 1,
+       /* point-to-plane: the residual n . (p - q) with q's normal n (pcl::IterativeClosestPointWithNormals /
+        * TransformationEstimationPointToPlaneLLS; libwave's ICPMatcher has no counterpart: an opt-in) */
+       WM_ICP_PLANE = 2 };
 enum { WM_NN_AUTO = 0, WM_NN_GRID = 1, WM_NN_BRUTE = 2,
        /* wm_nn_search only, OR-ed in: seed every query with the point it matched in the previous
         * search of the same clouds (what consecutive ICP iterations do); same result, less work */
@@ -95,7 +98,10 @@ enum { /* pcl::registration::DefaultConvergenceCriteria::ConvergenceState */
        WM_CONV_ABS_MSE = 3,
        WM_CONV_REL_MSE = 4,
        WM_CONV_NO_CORRESPONDENCES = 5,
-       WM_CONV_FORCED = 6 };
+       WM_CONV_FORCED = 6,
+       /* WM_ICP_PLANE only (no PCL counterpart): J^T J of an iteration is singular to rounding -- the matched normals
+        * leave a motion free (one plane: three).  The align ends NOT converged, T_out untouched: loud, not wrong */
+       WM_CONV_DEGENERATE = 7 };
 
 typedef struct {
     double max_corr;      /* ICPMatcherParams::max_corr, icp.hpp:35 -> icp.cpp:47 */
@@ -104,13 +110,19 @@ typedef struct {
     double fit_eps;       /* ICPMatcherParams::fit_eps,  icp.hpp:43 -> icp.cpp:50 */
     int force_iterations; /* >0: run exactly this many iterations (bench; no stop tests) */
     int mode;             /* WM_ICP_SVD: PCL's Umeyama step (parity default);
-                             WM_ICP_GN6: 6x6 J^T J / J^T r Gauss-Newton step */
+                             WM_ICP_GN6: 6x6 J^T J / J^T r Gauss-Newton step;
+                             WM_ICP_PLANE: the same 6x6 step on the point-to-plane residual, with normals
+                             of the target estimated on the device once per target (wm_estimate_normals);
+                             the stopping rules and their MSE (mean point-to-point d^2) are unchanged.
+                             wm_icp_align, wm_icp_match and wm_icp_batch_match (every item through
+                             wm_icp_match inside the call: correct, not fast) take it; the sharded entry
+                             points (wm_icp_shard_*, wm_icp_*_sharded, wm_multi_*) return WM_ERR_ARG */
     int nn_method;        /* WM_NN_AUTO | WM_NN_GRID | WM_NN_BRUTE */
     int carry_state;      /* 1: seed the criteria's previous MSE from the ctx (PCL keeps
                              it across align() calls on one object); 0: fresh */
     int profile;          /* HIP-event timing on the ctx stream: 1 = the level-0
                              correspondence kernel only; 2 = every kernel class */
-    int reserved;
+    int normal_k;         /* WM_ICP_PLANE: neighbours per normal, 3 ... 32; 0 = the default, 20 */
 } wm_icp_params;
 
 typedef struct {
@@ -315,10 +327,24 @@ int wm_get_correspondences(wm_ctx *ctx, int32_t *match_idx, float *d2, size_t ca
 int wm_nn_search(wm_ctx *ctx, const double T[16], double max_corr, int nn_method,
                  int32_t *match_idx, float *d2, size_t cap, float *kernel_ms);
 
+/* Normals of the context's target (which = 1) or source (which = 0), mirroring wm_gicp_covariances: per point the
+ * k nearest points of the same cloud, the point itself included (the neighbourhood of computeCovariances, same tie
+ * order: distance, then index), their covariance in double about the neighbourhood mean, the unit eigenvector of its
+ * smallest eigenvalue turned towards the origin (pcl::flipNormalTowardsViewpoint with the viewpoint at 0: n . p <= 0)
+ * and the curvature lambda0 / (lambda0 + lambda1 + lambda2) -- pcl::NormalEstimation with setKSearch(k).  normals_out:
+ * float x 4 (nx, ny, nz, curvature) per input point in the caller's order, in host or device memory (`out_mem`).  A
+ * non-finite point, or a neighbourhood whose largest eigenvalue is 0, gives (0, 0, 0, 0).  k: 3 ... 32, 0 = the
+ * default, 20.  WM_NOT_CONVERGED when the cloud has fewer than k finite points.  The target's normals stay on the
+ * context (what a WM_ICP_PLANE align with the same k uses) until the target changes. */
+int wm_estimate_normals(wm_ctx *ctx, int which, int k, void *normals_out, int out_mem);
+
 /* The sufficient statistics one ICP iteration reduces to (what crosses xGMI in
  * the multi-GPU path).  SVD mode: stats[0]=n, [1..3]=sum p, [4..6]=sum q,
  * [7..15]=sum q p^T (row-major), [16]=sum d2.  GN6 mode: [0]=n, [1]=sum d2,
- * [2..22]=upper triangle of J^T J (row-major), [23..28]=J^T r.  Both: [31] = number of
+ * [2..22]=upper triangle of J^T J (row-major), [23..28]=J^T r.  PLANE mode: the GN6 layout with the rows
+ * J = [n^T, (p x n)^T] and r = n . (p - q) (n: the matched point's normal on the context -- those of the last plane
+ * align or wm_estimate_normals, else estimated with the default k; a pair whose normal is zero adds to [0], [1] only).
+ * All: [31] = number of
  * source points this context handled (== cloud size unless sharded).  Uses the
  * correspondences of the last wm_nn_search / align iteration. */
 #define WM_STATS_LEN 32

@@ -22,13 +22,14 @@ WM_BATCH_MAX_TARGET_POINTS = 65535  # larger ones (up to this) in HBM scratch
 WM_GROUND_BATCH_MAX_KEYS = 0xFFFFFFFF  # n_scans * (num_bins_a * num_bins_l + 1) of a ground_segment_batch
 WM_GROUND_BATCH_MAX_POINTS = 0x7FFFFFF0  # its scans' points in all
 WM_MEM_HOST, WM_MEM_DEVICE = 0, 1
-WM_ICP_SVD, WM_ICP_GN6 = 0, 1
+WM_ICP_SVD, WM_ICP_GN6, WM_ICP_PLANE = 0, 1, 2
 WM_NN_AUTO, WM_NN_GRID, WM_NN_BRUTE = 0, 1, 2
 WM_NN_WARM = 0x100
 WM_INFO_LUM, WM_INFO_CENSI, WM_INFO_LUMOLD = 0, 1, 2
 WM_STATS_LEN = 32
 CONV_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
-              5: "NO_CORRESPONDENCES", 6: "FORCED"}
+              5: "NO_CORRESPONDENCES", 6: "FORCED", 7: "DEGENERATE"}
+WM_CONV_DEGENERATE = 7
 
 
 class WmError(RuntimeError):
@@ -39,7 +40,7 @@ class IcpParams(C.Structure):
     _fields_ = [("max_corr", C.c_double), ("max_iter", C.c_int), ("t_eps", C.c_double),
                 ("fit_eps", C.c_double), ("force_iterations", C.c_int), ("mode", C.c_int),
                 ("nn_method", C.c_int), ("carry_state", C.c_int), ("profile", C.c_int),
-                ("reserved", C.c_int)]
+                ("normal_k", C.c_int)]
 
 
 class IcpStats(C.Structure):
@@ -237,6 +238,7 @@ def lib():
         L.wm_get_correspondences.argtypes = [C.c_void_p, _ip, _fp, C.c_size_t]
         L.wm_nn_search.argtypes = [C.c_void_p, _dp, C.c_double, C.c_int, _ip, _fp, C.c_size_t, _fp]
         L.wm_icp_stats_for.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
+        L.wm_estimate_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.wm_umeyama_from_stats.argtypes = [_dp, _dp]
         L.wm_gn6_from_stats.argtypes = [_dp, _dp]
         L.wm_ground_default_params.argtypes = [C.POINTER(GroundParams)]
@@ -677,6 +679,21 @@ class Context:
         self._check(lib().wm_gicp_covariances(self._h, int(k), float(eps), cs.ctypes.data_as(_dp),
                                               ct.ctypes.data_as(_dp)), "wm_gicp_covariances")
         return cs, ct
+
+    def estimate_normals(self, which=1, k=0, out=None):
+        """wm_estimate_normals: (nx, ny, nz, curvature) per point of the target (which = 1) or the source (0), caller
+        order; k = 0: the default, 20.  out: a float32 CUDA tensor of shape (n, 4) to fill on the device; None: a numpy
+        array is returned."""
+        n = self.n_tgt if which == 1 else self.n_src
+        if out is None:
+            res = np.zeros((n, 4), np.float32)
+            self._check(lib().wm_estimate_normals(self._h, int(which), int(k), C.c_void_p(res.ctypes.data), WM_MEM_HOST),
+                        "wm_estimate_normals")
+            return res
+        assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, 4) and out.element_size() == 4
+        self._check(lib().wm_estimate_normals(self._h, int(which), int(k), C.c_void_p(out.data_ptr()), WM_MEM_DEVICE),
+                    "wm_estimate_normals")
+        return out
 
     # ---- NDT
     def ndt_align(self, params=None, **kw):

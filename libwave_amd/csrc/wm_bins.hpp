@@ -80,15 +80,22 @@ __device__ __host__ inline double bins_value(long long L0, long long L1, long lo
 // ---- the reading side: the bins' words added up (integers: exact in any order) and set back to zero, by ALL THREADS
 // threads of ONE workgroup (THREADS >= 4 x 57); afterwards -- a barrier has been passed -- B.tot[c] is component c as a
 // double ([kAcc]: the searched-queries count) and B.poison says whether a sum did not fit the limbs.
-struct BinsLds {
-    long long part[4][kBinLimbs * kBinComps];
-    double tot[kBinComps];
+// (COMPS components of a bin are in use, the first VALUES of them sums in limbs, the rest plain counts in limb 0: the ICP
+// loop's kBinComps / kAcc, or the point-to-plane pass's 29 / 29, wm_plane.hip -- whose 87 words per bin leave a
+// 256-thread workgroup two groups of threads, not four)
+template <int COMPS>
+struct BinsLdsT {
+    long long part[4][kBinLimbs * COMPS];
+    double tot[COMPS];
     unsigned poison;
 };
-template <int THREADS>
-__device__ __forceinline__ void bins_collect(long long *__restrict__ bins, BinsLds &B) {
+using BinsLds = BinsLdsT<kBinComps>;
+template <int THREADS, int COMPS = kBinComps, int VALUES = kAcc>
+__device__ __forceinline__ void bins_collect(long long *__restrict__ bins, BinsLdsT<COMPS> &B) {
+    static_assert(COMPS < (int) kBinPoison && VALUES <= COMPS, "components below the poison word");
+    constexpr int kBinComps = COMPS, kAcc = VALUES;       // (this function's own: the names below are the template's)
     constexpr int kWordsPerBin = kBinLimbs * kBinComps;  // 57 words of a bin are in use
-    constexpr int kGroups = 4;                            // groups of threads, kBinCount / 4 bins each
+    constexpr int kGroups = THREADS >= 4 * kWordsPerBin ? 4 : 2;  // groups of threads, kBinCount / kGroups bins each
     static_assert(THREADS >= kGroups * kWordsPerBin && kBinCount % kGroups == 0, "bins per thread group");
     constexpr int kPer = kBinCount / kGroups;
     const unsigned g = threadIdx.x / (unsigned) kWordsPerBin, j = threadIdx.x % (unsigned) kWordsPerBin;

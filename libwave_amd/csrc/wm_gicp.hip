@@ -892,6 +892,35 @@ static int launch_cov_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n
     return launch_cov<32>(ctx, g, q, n, orig, k, eps, out, by_w);
 }
 
+// the source's own grid (the target's is the level-0 search grid): what the k-NN of its covariances and normals scans
+int source_grid(wm_ctx *ctx) {
+    double occ = 0, vol = 1;
+    for (int d = 0; d < 3; ++d) vol *= fmax((double) ctx->src_bbox.hi[d] - ctx->src_bbox.lo[d], 1e-3);
+    float h = choose_cell(ctx->src_bbox, ctx->n_src);
+    // a source like the previous one (consecutive scans of one sensor): start from the cell
+    // size that was tuned for it, which usually passes the occupancy check at once and saves
+    // the second build (the level-0 grid of the target does the same)
+    bool trust = false;  // a cloud this close to the one the cell size was measured on: no occupancy check
+                         // (a device -> host round trip) -- but look again every 16th time, as build_level0 does
+    if (ctx->tuned_src_h > 0 && ctx->tuned_src_n > 0) {
+        const double rn = (double) ctx->n_src / (double) ctx->tuned_src_n, rv = vol / ctx->tuned_src_vol;
+        if (rn > 0.8 && rn < 1.25 && rv > 0.6 && rv < 1.6) h = (float) ctx->tuned_src_h;
+        trust = rn > 0.9 && rn < 1.1 && rv > 0.8 && rv < 1.25 && ++ctx->tuned_src_uses < 16;
+    }
+    if (!trust) ctx->tuned_src_uses = 0;
+    WM_TRY(build_grid_level(ctx, ctx->src_orig.as<float4>(), ctx->n_src_input, ctx->src_bbox, h,
+                            &ctx->src_grid, trust ? nullptr : &occ));
+    if (occ > 6.0 || (occ > 0 && occ < 1.5)) {
+        h = (float) (h * sqrt(3.0 / occ));
+        WM_TRY(build_grid_level(ctx, ctx->src_orig.as<float4>(), ctx->n_src_input, ctx->src_bbox, h,
+                                &ctx->src_grid, nullptr));
+    }
+    ctx->tuned_src_h = h;
+    ctx->tuned_src_n = ctx->n_src;
+    ctx->tuned_src_vol = vol;
+    return WM_OK;
+}
+
 static int compute_covariances(wm_ctx *ctx, int k, double eps) {
     if (k > 32) return WM_ERR_ARG;
     const bool same = ctx->gicp_cov_k == k && ctx->gicp_cov_eps == eps;
@@ -929,30 +958,7 @@ static int compute_covariances(wm_ctx *ctx, int k, double eps) {
     if (!(ctx->gicp_cov_src_valid && same)) {
         // source: its own grid; covariances stored in Morton (src_sorted) order
         WM_HIP(ctx, ctx->gicp_c1.reserve((ctx->n_src > 0 ? ctx->n_src : 1) * 9 * sizeof(double)));
-        double occ = 0, vol = 1;
-        for (int d = 0; d < 3; ++d) vol *= fmax((double) ctx->src_bbox.hi[d] - ctx->src_bbox.lo[d], 1e-3);
-        float h = choose_cell(ctx->src_bbox, ctx->n_src);
-        // a source like the previous one (consecutive scans of one sensor): start from the cell
-        // size that was tuned for it, which usually passes the occupancy check at once and saves
-        // the second build (the level-0 grid of the target does the same)
-        bool trust = false;  // a cloud this close to the one the cell size was measured on: no occupancy check
-                             // (a device -> host round trip) -- but look again every 16th time, as build_level0 does
-        if (ctx->tuned_src_h > 0 && ctx->tuned_src_n > 0) {
-            const double rn = (double) ctx->n_src / (double) ctx->tuned_src_n, rv = vol / ctx->tuned_src_vol;
-            if (rn > 0.8 && rn < 1.25 && rv > 0.6 && rv < 1.6) h = (float) ctx->tuned_src_h;
-            trust = rn > 0.9 && rn < 1.1 && rv > 0.8 && rv < 1.25 && ++ctx->tuned_src_uses < 16;
-        }
-        if (!trust) ctx->tuned_src_uses = 0;
-        WM_TRY(build_grid_level(ctx, ctx->src_orig.as<float4>(), ctx->n_src_input, ctx->src_bbox, h,
-                                &ctx->src_grid, trust ? nullptr : &occ));
-        if (occ > 6.0 || (occ > 0 && occ < 1.5)) {
-            h = (float) (h * sqrt(3.0 / occ));
-            WM_TRY(build_grid_level(ctx, ctx->src_orig.as<float4>(), ctx->n_src_input, ctx->src_bbox, h,
-                                    &ctx->src_grid, nullptr));
-        }
-        ctx->tuned_src_h = h;
-        ctx->tuned_src_n = ctx->n_src;
-        ctx->tuned_src_vol = vol;
+        WM_TRY(source_grid(ctx));
         const float4 *q = ctx->src_sorted.as<float4>();
         WM_TRY(launch_cov_k(ctx, ctx->src_grid.d, q, ctx->n_src, ctx->src_orig.as<float4>(), k, eps,
                             ctx->gicp_c1.as<double>(), 0));

@@ -170,25 +170,6 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
-// What the host steers by while it runs ahead of the device (wm_icp_align): one 8-byte word in pinned memory -- done
-// flag, iterations finished, the step's size -- in ONE system-scope store (pub[0]: the latest; pub[k]: iteration k's
-// own record, so that what the host decides from does not depend on when it looks).
-__device__ __forceinline__ void publish_step(const IcpDevState *s, unsigned long long *pub, int pub_slots) {
-    if (!pub) return;
-    // [iteration : 16 | step size as bfloat16 : 16 | changed matches : 16 | searched by the certificate kernel : 16]
-    // -- fractions in 1 / 65535
-    const unsigned f_ch = (unsigned) (fminf(fmaxf(s->frac_changed, 0.f), 1.f) * 65535.f + 0.5f);
-    const unsigned f_un = (unsigned) (fminf(fmaxf(s->frac_unsettled, 0.f), 1.f) * 65535.f + 0.5f);
-    const unsigned long long w = ((unsigned long long) ((unsigned) s->iter & 0xFFFFu) << 48) |
-                                 ((unsigned long long) (__float_as_uint(s->step_disp) >> 16) << 32) |
-                                 ((unsigned long long) f_ch << 16) | (unsigned long long) f_un;
-    if (s->iter >= 1 && s->iter <= pub_slots) __hip_atomic_store(pub + s->iter, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // ([0]: bit 0 = done, above it the number of iterations finished by then -- ONE word, so that a host that sees
-    // `done` before the last record knows whether that record is still to come)
-    __hip_atomic_store(pub, s->done ? (1ull | ((unsigned long long) (unsigned) s->iter << 1)) : 0ull, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // The iteration's solve from the BINS the search kernel's waves added their sums into (wm_bins.hpp): the unsharded
 // loop's replacement for k_reduce_rows + k_reduce_solve<3>.  One workgroup: thread (g, j) adds word j (limb, component)
 // of bins g, g + kGroups, ... -- integers: exact in any order --, the kGroups partial totals meet in LDS, one thread per
@@ -1101,7 +1082,8 @@ void wm_ctx_destroy(wm_ctx *ctx) {
                       &ctx->ds_tgt, &ctx->match_ref, &ctx->match_tgt,
                       &ctx->partials, &ctx->partials2, &ctx->bins, &ctx->nn_bound, &ctx->late_ctl, &ctx->cert_count, &ctx->cert_prof, &ctx->cost_log, &ctx->phase_log, &ctx->shard_ref, &ctx->shard_tgt,
                       &ctx->shard_ref_band, &ctx->shard_tgt_band, &ctx->shard_misc, &ctx->shard_flags, &ctx->shard_pos_t,
-                      &ctx->shard_pos_s, &ctx->shard_stats, &ctx->ndt_sum_dev, &ctx->corr_tmp_idx, &ctx->corr_tmp_d2, &ctx->d_state};
+                      &ctx->shard_pos_s, &ctx->shard_stats, &ctx->ndt_sum_dev, &ctx->corr_tmp_idx, &ctx->corr_tmp_d2, &ctx->d_state,
+                      &ctx->plane_nrm, &ctx->plane_nrm_src, &ctx->plane_bins};
     for (DevBuf *b : bufs) b->release();
     ctx->icp_stage.release();
     ctx->gicp_stage.release();
@@ -1181,6 +1163,7 @@ int wm_set_target(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem
     ctx->have_corr = false;
     ctx->ndt_built = false;
     ctx->gicp_cov_tgt_valid = false;
+    ctx->plane_nrm_valid = false;
     ctx->n_tgt_input = n;
     ctx->n_tgt = 0;
     ctx->tgt_pending = false;
@@ -1245,8 +1228,9 @@ void wm_icp_default_params(wm_icp_params *p) {
 
 int wm_icp_align(wm_ctx *ctx, const wm_icp_params *p, double T_out[16], wm_icp_stats *stats) {
     if (!ctx || !p || !T_out) return WM_ERR_ARG;
-    if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6)) return WM_ERR_ARG;
+    if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6 && p->mode != WM_ICP_PLANE)) return WM_ERR_ARG;
     if (p->force_iterations <= 0 && p->max_iter <= 0) return WM_ERR_ARG;
+    if (p->mode == WM_ICP_PLANE && (plane_normal_k(p->normal_k) < 3 || plane_normal_k(p->normal_k) > 32)) return WM_ERR_ARG;
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (ctx->n_src_input == 0 || ctx->n_tgt_input == 0) {
@@ -1263,6 +1247,13 @@ int wm_icp_align(wm_ctx *ctx, const wm_icp_params *p, double T_out[16], wm_icp_s
     WM_TRY(prepare_work(ctx));
     const bool brute = use_brute(ctx, p->nn_method);
     if (!brute) WM_TRY(ensure_levels(ctx, p->max_corr));
+    if (p->mode == WM_ICP_PLANE) {
+        // the target's normals, once per target (and k): cached on the context until wm_set_target
+        const int rc = plane_target_normals(ctx, p->normal_k);
+        if (rc == WM_NOT_CONVERGED && stats) stats->state = WM_CONV_NO_CORRESPONDENCES;  // fewer target points than neighbours
+        if (rc != WM_OK) return rc == WM_NOT_CONVERGED ? WM_TOO_FEW_CORRESPONDENCES : rc;
+        WM_TRY(plane_bins_ready(ctx));
+    }
     const float thr = threshold_d2(p->max_corr);
     double I[16];
     mat4_identity(I);
@@ -1310,8 +1301,11 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
     }
     // (nothing of an earlier align is in flight: each ends with a fetch of the state)
     memset(ctx->h_pub, 0, sizeof(unsigned long long) * (size_t) (max_it + 1));
+    // point-to-plane (wm_plane.hip): a search-only launch, the plane sums, their solve.  Always the FULL search: the
+    // certificate kernel's policy is steered by counts only the fused statistics carry.
+    const bool plane = p->mode == WM_ICP_PLANE;
     const bool can_cert = !brute && ctx->tune_nn_balanced && ctx->tune_cert_from >= -1 &&
-                          ctx->n_tgt_input < (1u << 26) - 8u && !ctx->cost_log.p;
+                          ctx->n_tgt_input < (1u << 26) - 8u && !ctx->cost_log.p && !plane;
     volatile unsigned long long *pub = ctx->h_pub;
     bool cert_on = false, bounds_valid = false, seen_done = false;
     const float cert_thr = brute ? 0.f : ctx->tune_cert_disp * ctx->levels[0].d.h;
@@ -1323,7 +1317,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
     ctx->cert_launches = 0;
     // the grid path adds its sums into bins (wm_bins.hpp) and solves from them -- k_bins_solve, or, sharded, the
     // k_reduce_solve that carries the exchange: no k_reduce_rows, no rows of partial sums
-    const bool use_bins = !brute && ctx->tune_bins != 0 && !ctx->cost_log.p;
+    const bool use_bins = !brute && ctx->tune_bins != 0 && !ctx->cost_log.p && !plane;
     if (use_bins) {
         WM_TRY(bins_ready(ctx));  // (zeroes them if the last loop left them dirty)
         ctx->bins_dirty = true;   // (until this loop has ended normally)
@@ -1531,6 +1525,18 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
             }
         }
         unsigned rows = (unsigned) nb;
+        if (plane) {
+            if (blk) return WM_ERR_ARG;  // (not sharded: the entry points refuse the mode)
+            if (brute) WM_TRY(launch_nn_brute(ctx, thr, e0, e1));
+            else WM_TRY(launch_nn_grid(ctx, thr, e0, e1, e1b, -1, nullptr, false));
+            if (brute && e1b) WM_HIP(ctx, hipEventRecord(e1b, ctx->stream));
+            WM_TRY(launch_plane_stats(ctx));
+            if (e2) WM_HIP(ctx, hipEventRecord(e2, ctx->stream));
+            WM_TRY(launch_plane_solve(ctx, ctx->h_pub, ctx->h_pub_slots, 1));
+            if (e3) WM_HIP(ctx, hipEventRecord(e3, ctx->stream));
+            WM_HIP(ctx, hipGetLastError());
+            continue;
+        }
         if (brute) {
             WM_TRY(launch_nn_brute(ctx, thr, e0, e1));
             if (e1b) WM_HIP(ctx, hipEventRecord(e1b, ctx->stream));
@@ -1626,7 +1632,7 @@ int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, wm_
         (void) hipEventElapsedTime(&stats->align_ms, ctx->ev_a, ctx->ev_b);
         if (p->profile) {
             // iterations that ran (the rest of the last batch were no-ops)
-            const int ran = s.iter + (s.state == WM_CONV_NO_CORRESPONDENCES ? 1 : 0);
+            const int ran = s.iter + (s.state == WM_CONV_NO_CORRESPONDENCES || s.state == WM_CONV_DEGENERATE ? 1 : 0);
             for (int it = 0; it < ran && (size_t) it < ev_slot.size(); ++it) {
                 if (ev_slot[(size_t) it] < 0 || (size_t) (ev_slot[(size_t) it] + 4) >= ev_used) {
                     ctx->iter_nn_ms.push_back(-1.f);  // (ran inside the resident kernel: no launch of its own)
@@ -1829,6 +1835,7 @@ int wm_icp_shard_begin(wm_ctx *ctx, const wm_icp_params *p, double x_lo, double 
     // (an empty slab, x_lo == x_hi, and an empty band of the source are legitimate for a rank of a
     // sharded registration: it contributes zeros)
     if (!ctx || !p || !(p->max_corr > 0) || !(x_lo <= x_hi)) return WM_ERR_ARG;
+    if (p->mode == WM_ICP_PLANE) return WM_ERR_ARG;  // (the plane metric is not sharded)
     if (ctx->n_src_input == 0 && expect_owned_total == 0) return WM_ERR_STATE;
     WM_TRY(shard_begin(ctx, p, x_lo, x_hi, (double) expect_owned_total, 0.0, nullptr, nullptr, DBL_MAX));
     WM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2149,7 +2156,7 @@ int wm_nn_search(wm_ctx *ctx, const double T[16], double max_corr, int nn_method
 }
 
 int wm_icp_stats_for(wm_ctx *ctx, const double T[16], int mode, double stats[WM_STATS_LEN]) {
-    if (!ctx || !T || !stats || (mode != WM_ICP_SVD && mode != WM_ICP_GN6)) return WM_ERR_ARG;
+    if (!ctx || !T || !stats || (mode != WM_ICP_SVD && mode != WM_ICP_GN6 && mode != WM_ICP_PLANE)) return WM_ERR_ARG;
     if (!ctx->have_corr) return WM_ERR_STATE;
     WM_HIP(ctx, hipSetDevice(ctx->device));
     WM_TRY(prepare_work(ctx));
@@ -2158,6 +2165,16 @@ int wm_icp_stats_for(wm_ctx *ctx, const double T[16], int mode, double stats[WM_
     p.mode = mode;
     init_state(ctx->h_state, T, &p, DBL_MAX);
     WM_TRY(upload_state(ctx));
+    if (mode == WM_ICP_PLANE) {
+        // the normals the context holds (those of the last plane align or wm_estimate_normals); none yet: the default k
+        WM_TRY(plane_target_normals(ctx, ctx->plane_nrm_valid ? ctx->plane_nrm_k : 0));
+        WM_TRY(plane_bins_ready(ctx));
+        WM_TRY(launch_plane_stats(ctx));
+        WM_TRY(launch_plane_solve(ctx, nullptr, 0, 0));
+        WM_TRY(download_state(ctx));
+        memcpy(stats, ctx->h_state->stats, sizeof(double) * WM_STATS_LEN);
+        return WM_OK;
+    }
     WM_TRY(launch_stats(ctx, mode));
     WM_TRY(launch_reduce_solve<1>(ctx, (unsigned) stat_blocks(ctx->n_src), nullptr));
     WM_TRY(download_state(ctx));

@@ -381,6 +381,12 @@ struct wm_ctx {
     int gicp_cov_k = 0;
     double gicp_cov_eps = 0;
 
+    // point-to-plane ICP (wm_plane.hip): the target's normals (float4 nx ny nz curvature, caller order), valid until the
+    // target changes; the source's of the last wm_estimate_normals; the plane pass's own bins (29 components)
+    wm::DevBuf plane_nrm, plane_nrm_src, plane_bins;
+    bool plane_nrm_valid = false;
+    int plane_nrm_k = 0;
+
     // NDT voxel model of the target
     wm::DevBuf ndt_keys, ndt_keys2, ndt_vox, ndt_vkey, ndt_hkeys, ndt_hvals, ndt_dense, ndt_meanf, ndt_vsum;
     bool ndt_dense_on = false;  // dense cell -> voxel-slot table built (small lattices)
@@ -560,6 +566,16 @@ int batch_match_scaled(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
                        double *info_out, wm_icp_stats *stats, int *status);
 float threshold_d2(double max_corr);
 float threshold_d2_strict(double max_corr);
+
+// ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
+constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0
+int plane_normal_k(int k);          // 0 -> the default
+int plane_target_normals(wm_ctx *ctx, int k);  // the target's normals on the context (cached per target and k)
+int plane_bins_ready(wm_ctx *ctx);
+int launch_plane_stats(wm_ctx *ctx);  // after a search-only launch: the 29 sums into the plane bins
+int launch_plane_solve(wm_ctx *ctx, unsigned long long *pub, int pub_slots, int solve);  // solve == 0: the sums into st->stats only
+// ---- wm_gicp.hip
+int source_grid(wm_ctx *ctx);  // the source's own search grid (ctx->src_grid), built over src_orig
 
 // ---- wm_icp.hip
 int shard_begin(wm_ctx *ctx, const wm_icp_params *p, double x_lo, double x_hi, double expect, double stripe_finite,

@@ -985,10 +985,41 @@ int wm_icp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
                        const wm_icp_params *p, float res, int multiscale_steps, int with_info, double *T_out,
                        double *info_out, wm_icp_stats *stats, int *status) {
     if (!ctx || !p || !status || n_items < 0 || (n_items > 0 && !items) || stride < 12 || (stride & 3)) return WM_ERR_ARG;
-    if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6)) return WM_ERR_ARG;
+    if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6 && p->mode != WM_ICP_PLANE)) return WM_ERR_ARG;
     if (p->force_iterations <= 0 && p->max_iter <= 0) return WM_ERR_ARG;
     if (with_info != 0 && with_info != 1) return WM_ERR_ARG;
     if (n_items == 0) return WM_OK;
+    if (p->mode == WM_ICP_PLANE) {
+        // the one-workgroup registrations know no normals: every item is registered by wm_icp_match inside the call, the
+        // route oversize items take -- correct, not fast
+        for (int k = 0; k < n_items; ++k) {
+            const wm_batch_item &it = items[k];
+            if ((it.n_src > 0 && !it.src) || (it.n_target > 0 && !it.target) || it.n_src > 0x7FFFFFF0u || it.n_target > 0x7FFFFFF0u)
+                return WM_ERR_ARG;
+        }
+        for (int k = 0; k < n_items; ++k) {
+            // fresh stopping criteria per item; its SCALES carry the last MSE from one align to the next (batch_match_scaled's
+            // one-by-one route, wm_batch.hip)
+            wm_icp_params one = *p;
+            one.carry_state = 1;
+            ctx->prev_mse = -1;
+            const wm_batch_item &it = items[k];
+            double T[16];
+            wm_icp_stats st;
+            const int rc = wm_icp_match(ctx, it.src, it.n_src, it.target, it.n_target, stride, mem, &one, res, multiscale_steps, T, &st);
+            if (rc < 0 && rc != WM_ERR_STATE) return rc;  // (WM_ERR_STATE: an item of two empty clouds, as the batched path reports it)
+            status[k] = rc;
+            if (stats) stats[k] = st;
+            if (rc == WM_OK && T_out) memcpy(T_out + 16 * (size_t) k, T, sizeof(T));
+            if (with_info && info_out && rc >= 0) {  // estimateLUMold on the clouds of the item's last align, whatever match() returned
+                double info[36];
+                int deg = 0;
+                if (wm_icp_info(ctx, WM_INFO_LUMOLD, nullptr, 0, 0, p->max_corr, info, &deg) == WM_OK)
+                    memcpy(info_out + 36 * (size_t) k, info, sizeof(info));
+            }
+        }
+        return WM_OK;
+    }
     for (int k = 0; k < n_items; ++k) {
         const wm_batch_item &it = items[k];
         if ((it.n_src > 0 && !it.src) || (it.n_target > 0 && !it.target) || it.n_src > 0x7FFFFFF0u || it.n_target > 0x7FFFFFF0u)

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "shim.hpp"
 
@@ -39,6 +40,26 @@ int benchForceIterations() {
 }  // namespace
 void ICPMatcher::setBenchForceIterations(int n) { benchForceSetting().store(n > 0 ? n : 0); }
 
+namespace {
+// the error metric of matchers that were not told (ICPMatcher::setErrorMetric): env WAVE_ICP_ERROR_METRIC=plane
+int envErrorMetric() {
+    static const int v = [] {
+        const char *e = std::getenv("WAVE_ICP_ERROR_METRIC");
+        return e && std::string(e) == "plane" ? WM_ICP_PLANE : WM_ICP_SVD;
+    }();
+    return v;
+}
+}  // namespace
+
+void ICPMatcher::setErrorMetric(ErrorMetric m) { errorMetric = m == ErrorMetric::PointToPlane ? WM_ICP_PLANE : WM_ICP_SVD; }
+
+ICPMatcher::ErrorMetric ICPMatcher::getErrorMetric() const {
+    const int m = errorMetric >= 0 ? errorMetric : envErrorMetric();
+    return m == WM_ICP_PLANE ? ErrorMetric::PointToPlane : ErrorMetric::PointToPoint;
+}
+
+void ICPMatcher::setNormalK(int k) { normalK = k; }
+
 ICPMatcherParams::ICPMatcherParams(const std::string &config_path) {
     int estimator = 0;
     // `fit_eps` is deliberately absent: the reference's loader never reads it (icp.cpp:9-16)
@@ -67,7 +88,8 @@ ICPMatcher::ICPMatcher(ICPMatcherParams params1)
 // reference class, a context belongs to one object (and is created by the thread that uses it).
 ICPMatcher::ICPMatcher(const ICPMatcher &o)
     : Matcher<PCLPointCloudPtr>(o), params(o.params), ctx(nullptr), multi(nullptr), devices(o.devices),
-      device(o.device), converged(false), lastMatch(kNone), ref(o.ref), target(o.target) {}
+      device(o.device), converged(false), lastMatch(kNone), ref(o.ref), target(o.target), errorMetric(o.errorMetric),
+      normalK(o.normalK) {}
 
 ICPMatcher &ICPMatcher::operator=(const ICPMatcher &o) {
     if (this == &o) return *this;
@@ -82,6 +104,8 @@ ICPMatcher &ICPMatcher::operator=(const ICPMatcher &o) {
     lastMatch = kNone;
     ref = o.ref;
     target = o.target;
+    errorMetric = o.errorMetric;
+    normalK = o.normalK;
     return *this;
 }
 
@@ -118,6 +142,8 @@ bool ICPMatcher::match() {
     p.t_eps = params.t_eps;        // setTransformationEpsilon,      icp.cpp:49
     p.fit_eps = params.fit_eps;    // setEuclideanFitnessEpsilon,    icp.cpp:50
     p.carry_state = 1;             // one PCL object per matcher: its criteria remember the last MSE
+    p.mode = errorMetric >= 0 ? errorMetric : envErrorMetric();
+    p.normal_k = normalK;
     if (const int forced = benchForceIterations()) {  // (bench only: see setBenchForceIterations)
         p.force_iterations = forced;
         p.max_iter = std::max(p.max_iter, forced);
@@ -199,6 +225,8 @@ bool ICPMatcher::matchBatch(const std::vector<std::pair<PCLPointCloudPtr, PCLPoi
     p.max_iter = params.max_iter;
     p.t_eps = params.t_eps;
     p.fit_eps = params.fit_eps;
+    p.mode = errorMetric >= 0 ? errorMetric : envErrorMetric();
+    p.normal_k = normalK;
     const size_t n = pairs.size();
     std::vector<wm_batch_item> items(n);
     for (size_t k = 0; k < n; ++k) {
