@@ -714,6 +714,7 @@ static bool serve_eval(GicpFn &F, const FdfArgs &A) {
     const unsigned long long expect = ctx->gicp_serve_seq;
     volatile GicpSlot *slots = (volatile GicpSlot *) ctx->h_gicp_slots;
     int have = 0;  // slots 0 .. have - 1 carry this command's number
+    // (not host_wait: no yield stage, no blocking stage -- after 100 ms it falls back to launches instead of waiting on)
     for (unsigned spins = 1; have < kGicpAcc; ++spins) {
         while (have < kGicpAcc && slots[have].seq == expect) ++have;
         if (have == kGicpAcc) break;

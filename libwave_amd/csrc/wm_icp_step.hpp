@@ -7,6 +7,7 @@
 #define WM_ICP_STEP_HPP
 
 #include "wm_internal.hpp"
+#include "wm_icp_ctl.hpp"
 
 namespace wm {
 
@@ -193,21 +194,12 @@ __host__ __device__ inline void icp_apply_stats(IcpDevState *st, const double *s
 
 // What the host steers by while it runs ahead of the device (wm_icp_align): one 8-byte word in pinned memory -- done
 // flag, iterations finished, the step's size -- in ONE system-scope store (pub[0]: the latest; pub[k]: iteration k's
-// own record, so that what the host decides from does not depend on when it looks).
+// own record, so that what the host decides from does not depend on when it looks).  The words' layout: wm_icp_ctl.hpp.
 __device__ __forceinline__ void publish_step(const IcpDevState *s, unsigned long long *pub, int pub_slots) {
     if (!pub) return;
-    // [iteration : 16 | step size as bfloat16 : 16 | changed matches : 16 | searched by the certificate kernel : 16]
-    // -- fractions in 1 / 65535
-    const unsigned f_ch = (unsigned) (fminf(fmaxf(s->frac_changed, 0.f), 1.f) * 65535.f + 0.5f);
-    const unsigned f_un = (unsigned) (fminf(fmaxf(s->frac_unsettled, 0.f), 1.f) * 65535.f + 0.5f);
-    const unsigned long long w = ((unsigned long long) ((unsigned) s->iter & 0xFFFFu) << 48) |
-                                 ((unsigned long long) (__float_as_uint(s->step_disp) >> 16) << 32) |
-                                 ((unsigned long long) f_ch << 16) | (unsigned long long) f_un;
+    const unsigned long long w = pack_step_record(s->iter, s->step_disp, s->frac_changed, s->frac_unsettled);
     if (s->iter >= 1 && s->iter <= pub_slots) __hip_atomic_store(pub + s->iter, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    // ([0]: bit 0 = done, above it the number of iterations finished by then -- ONE word, so that a host that sees
-    // `done` before the last record knows whether that record is still to come)
-    __hip_atomic_store(pub, s->done ? (1ull | ((unsigned long long) (unsigned) s->iter << 1)) : 0ull, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(pub, pack_done_word(s->done, s->iter), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace wm

@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/wavematch.h"
@@ -258,7 +260,7 @@ struct wm_ctx {
     int n_levels = 0;
     double levels_max_corr = -1;
     float grid_cell_override = 0;
-    // ---- options (wm_icp.hip: kOptions names each one for wm_set_option and for the environment)
+    // ---- options (wm_ctx.hip: kOptions names each one for wm_set_option and for the environment)
     int trace = 0;               // WM_TRACE: progress lines on stderr
     // the grid search (wm_nn.hip)
     float tune_lane_lf = 0.2f;   // lane-serial scan: finest level with cell size >= this x radius
@@ -269,7 +271,7 @@ struct wm_ctx {
     int tune_nn_balanced = 1;    // search kernel: wave-pooled candidate trips (0: every lane walks its own)
     // the ICP loop
     int tune_lag = 2;            // iterations the host may run ahead of the device (icp_run_loop), 1 ... 16
-    int tune_spin_us = 80;       // wait_flag: busy-poll this long before polling with yields
+    int tune_spin_us = 80;       // host_wait: busy-poll this long before polling with yields
     int tune_bins = 1;           // 0: rows of partial sums + k_reduce_rows + k_reduce_solve, as up to round 5
     int tune_early_source = 2;   // a host target's upload overlaps the source's sort (wm_set_target); 2: and, from
                                  // pinned memory, starts on a copy engine before that sort is enqueued
@@ -418,17 +420,59 @@ struct wm_ctx {
 
 namespace wm {
 
-// ---- wm_grid.hip
-// (bbox_partials / bbox_blocks: the packed cloud's bounding-box partials as launch_bbox leaves them, in the same launch)
-int pack_cloud(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, float4 *out, int slot = 0, bool staged = false,
-               float *bbox_partials = nullptr, unsigned *bbox_blocks = nullptr);
-bool upload_begin_async(wm_ctx *ctx, const void *pts, size_t bytes);  // (pinned host memory: the copy starts now, see wm_grid.hip)
-int compute_bbox(wm_ctx *ctx, const float4 *pts, size_t n, Bbox *out, size_t *n_valid);
-// the two halves of compute_bbox: enqueue the reduction into `partials_dev` (kBboxBlocks * 8 floats),
-// and finish it on the host from the fetched partials
-constexpr int kBboxBlocks = 512;
-int launch_bbox(wm_ctx *ctx, const float4 *pts, size_t n, float *partials_dev, unsigned *blocks_out);
-void finish_bbox(const float *partials_host, unsigned blocks, Bbox *out, size_t *n_valid);
+// developer tracing (env WM_TRACE=1): drain the stream and print a marker, so that a GPU fault can
+// be pinned to the stage that was running
+#define WM_TRACE(ctx, what)                                                     \
+    do {                                                                        \
+        if ((ctx)->trace) {                                                     \
+            (void) hipStreamSynchronize((ctx)->stream);                         \
+            fprintf(stderr, "[wm] %s\n", what);                                 \
+            fflush(stderr);                                                     \
+        }                                                                       \
+    } while (0)
+
+// ---- host-side waits for a word the device writes into pinned memory
+// one turn of a host-side busy-wait (the pause hint of the host's architecture; nothing where there is none)
+static inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    __asm__ __volatile__("yield");
+#endif
+}
+// Wait until arrived() holds, in three stages.  Spin (most waits are tens of microseconds); then, after tune_spin_us,
+// poll with a yield between looks, so that worker threads sharing a core take turns instead of starving each other
+// (kernels of a few hundred microseconds: the NDT passes at 2M points); only after `block_after` let the runtime
+// block in hipStreamSynchronize -- its wake-up costs 0.1-0.2 ms on some hosts, which a registration that waits a
+// hundred times cannot afford, but it is the right thing for a wait of milliseconds and it is what reports a failed
+// kernel.  The clock is looked at every 64th spin, and between yields.
+// kWaitArrived: arrived() held; kWaitBlocked: everything enqueued has run, and the caller looks again (what it waits
+// for is there, unless a kernel ended without writing it); kWaitFailed: the runtime reported an error (last_error).
+enum HostWait { kWaitArrived, kWaitBlocked, kWaitFailed };
+template <class Pred>
+inline HostWait host_wait(wm_ctx *ctx, Pred arrived, std::chrono::milliseconds block_after) {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool yielding = false;
+    for (unsigned spins = 1; !arrived(); ++spins) {
+        if (yielding)
+            std::this_thread::yield();
+        else
+            cpu_relax();
+        if ((spins & 63u) == 0 || yielding) {
+            const auto waited = std::chrono::steady_clock::now() - t0;
+            if (waited > block_after) {
+                const hipError_t e = hipStreamSynchronize(ctx->stream);
+                if (e == hipSuccess) return kWaitBlocked;
+                ctx->last_error = std::string("hipStreamSynchronize(ctx->stream): ") + hipGetErrorString(e);
+                return kWaitFailed;
+            }
+            yielding = waited > std::chrono::microseconds(ctx->tune_spin_us);
+        }
+    }
+    return kWaitArrived;
+}
+
+// ---- wm_ctx.hip
 // Fetch what wm_set_source / wm_set_target left pending (bounding boxes, finite-point counts), then
 // Morton-sort the source on the side stream while -- when max_corr > 0 and the search will use the
 // grid -- the target's level ladder is built on the main stream; both are joined before returning.
@@ -439,11 +483,15 @@ void finish_bbox(const float *partials_host, unsigned blocks, Bbox *out, size_t 
 int finalize_clouds(wm_ctx *ctx, double max_corr = -1.0, int nn_method = 0, int sort_aside = 0);
 int join_source_sort(wm_ctx *ctx);
 int enqueue_deferred_sort(wm_ctx *ctx);
-int build_grid_level(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, float h,
-                     GridLevel *lvl, double *avg_occupancy);
-int morton_sort(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, size_t n_valid,
-                float4 *out);
-int ensure_levels(wm_ctx *ctx, double max_corr);
+int prepare_work(wm_ctx *ctx);  // keys, match points, partial rows and the iteration state for the source's size
+bool use_brute(const wm_ctx *ctx, int nn_method);  // all-pairs instead of the grid (WM_NN_AUTO: by the clouds' sizes)
+hipEvent_t get_event(wm_ctx *ctx, size_t k);       // event k of the context's pool (profile mode)
+// one correspondence pass with transform T; `predict` lets the search start from the
+// radii in the current keys
+int nn_pass(wm_ctx *ctx, const double T[16], float thr_d2, double max_corr, bool predict, bool slab = false,
+            float slab_lo = 0.f, float slab_hi = 0.f, bool wait = true);
+
+// ---- wm_fetch.hip
 // fetch a small result from device memory into pinned host memory and wait for it (copy, fence
 // and completion flag by one wavefront; see k_fetch_signal)
 int fast_fetch(wm_ctx *ctx, void *dst_pinned, const void *src_dev, size_t bytes);
@@ -466,28 +514,41 @@ inline int fast_fetch_custom(wm_ctx *ctx, Launch launch) {
 }
 // the same column sums left in DEVICE memory (no signal): what an all-reduce then works on
 int sum_to_device(wm_ctx *ctx, double *dst_dev, const double *src_dev, unsigned rows, unsigned k);
-// ---- wm_shard.hip: sum `n` doubles in device memory over the ranks of `comm`, on the context's stream
-int comm_allreduce(wm_ctx *ctx, struct wm_comm *comm, double *dev, int n);
-struct XchgDev;
-// WM_OK (and *out filled) when the communicator has mailboxes for the in-kernel exchange of the sharded loop's block
-int comm_exchange_args(struct wm_comm *comm, XchgDev *out);
-// developer tracing (env WM_TRACE=1): drain the stream and print a marker, so that a GPU fault can
-// be pinned to the stage that was running
-#define WM_TRACE(ctx, what)                                                     \
-    do {                                                                        \
-        if ((ctx)->trace) {                                                     \
-            (void) hipStreamSynchronize((ctx)->stream);                         \
-            fprintf(stderr, "[wm] %s\n", what);                                 \
-            fflush(stderr);                                                     \
-        }                                                                       \
-    } while (0)
 // pinned, device-visible host scratch of at least `bytes` (kernels write small results into it
 // through fast_fetch; the host reads them once its flag has arrived)
 void *pinned_scratch(wm_ctx *ctx, size_t bytes);
 // device -> caller (pageable) memory: drain the stream, then a blocking copy (the caller's pages
 // are pinned and unpinned by the runtime inside that one call)
 int copy_to_caller(wm_ctx *ctx, void *dst, const void *src_dev, size_t bytes);
+// Wait for everything enqueued on the context's stream WITHOUT burning a core: the batched paths wait
+// milliseconds per launch, and a crew of MultiMatcher workers that all spin through their waits
+// (hipStreamSynchronize busy-polls) exhausts a container's CPU quota -- the whole process is then
+// throttled, staging threads included.  The thread sleeps between looks at an event (wake-up ~0.1 ms).
+int sync_sleeping(wm_ctx *ctx);
+
+// ---- wm_grid.hip
+// (bbox_partials / bbox_blocks: the packed cloud's bounding-box partials as launch_bbox leaves them, in the same launch)
+int pack_cloud(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, float4 *out, int slot = 0, bool staged = false,
+               float *bbox_partials = nullptr, unsigned *bbox_blocks = nullptr);
+bool upload_begin_async(wm_ctx *ctx, const void *pts, size_t bytes);  // (pinned host memory: the copy starts now, see wm_grid.hip)
+int compute_bbox(wm_ctx *ctx, const float4 *pts, size_t n, Bbox *out, size_t *n_valid);
+// the two halves of compute_bbox: enqueue the reduction into `partials_dev` (kBboxBlocks * 8 floats),
+// and finish it on the host from the fetched partials
+constexpr int kBboxBlocks = 512;
+int launch_bbox(wm_ctx *ctx, const float4 *pts, size_t n, float *partials_dev, unsigned *blocks_out);
+void finish_bbox(const float *partials_host, unsigned blocks, Bbox *out, size_t *n_valid);
+int build_grid_level(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, float h,
+                     GridLevel *lvl, double *avg_occupancy);
+int morton_sort(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, size_t n_valid,
+                float4 *out);
+int ensure_levels(wm_ctx *ctx, double max_corr);
 int exclusive_scan(wm_ctx *ctx, const unsigned *in, size_t n, unsigned *out);
+
+// ---- wm_shard.hip: sum `n` doubles in device memory over the ranks of `comm`, on the context's stream
+int comm_allreduce(wm_ctx *ctx, struct wm_comm *comm, double *dev, int n);
+struct XchgDev;
+// WM_OK (and *out filled) when the communicator has mailboxes for the in-kernel exchange of the sharded loop's block
+int comm_exchange_args(struct wm_comm *comm, XchgDev *out);
 
 // ---- wm_voxel.hip
 // pcl::VoxelGrid on device: `in` is a packed float4 cloud (w = index, NaN = invalid);
@@ -507,7 +568,6 @@ int transform_cloud_dev(wm_ctx *ctx, const float4 *in, size_t n, const double T[
 // statistics of the iteration to *rows_out rows of kAcc doubles in ctx->partials
 int launch_nn_grid(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
                    int stats_mode = -1, unsigned *rows_out = nullptr, bool use_bins = false);
-int bins_ready(wm_ctx *ctx);  // wm_icp.hip: the iteration's bins (wm_bins.hpp) allocated and all zero
 int launch_nn_brute(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1);
 // the resident form of the certificate kernel (wm_nn.hip: k_nn_cert<.., LATE>): the late iterations in one launch
 bool late_possible(wm_ctx *ctx, int stats_mode, unsigned *blocks_out);
@@ -517,29 +577,15 @@ int launch_nn_late(wm_ctx *ctx, float thr_d2, int stats_mode, unsigned blocks, b
 // the device's budget of resident workgroups (per process), in 1/1024ths of the device: the share taken (0: refused)
 int resident_admit(int device, int nb, int capacity);
 void resident_release(int device, int share);
-// one turn of a host-side busy-wait (the pause hint of the host's architecture; nothing where there is none)
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    __asm__ __volatile__("yield");
-#endif
-}
-
-// Wait for everything enqueued on the context's stream WITHOUT burning a core: the batched paths wait
-// milliseconds per launch, and a crew of MultiMatcher workers that all spin through their waits
-// (hipStreamSynchronize busy-polls) exhausts a container's CPU quota -- the whole process is then
-// throttled, staging threads included.  The thread sleeps between looks at an event (wake-up ~0.1 ms).
-int sync_sleeping(wm_ctx *ctx);
 int launch_fix_keys(wm_ctx *ctx, float thr_d2);  // after certified iterations: every key's distance brought up to date
 // the certificate kernel (late iterations): stats_mode as above; bounds_valid = the previous search of
 // this align was launch_nn_cert too (its per-query bounds are still in ctx->nn_bound)
 int launch_nn_cert(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2, int stats_mode,
                    unsigned *rows_out, bool bounds_valid, bool use_bins = false);
-// wm_batch.hip: pcl::VoxelGrid of all the clouds of a batch in one pass (see there)
-int batch_voxel_filter(wm_ctx *ctx, const wm_batch_item *items, const std::vector<int> &idx, size_t stride, int mem, float leaf,
-                       const float4 **filtered, std::vector<unsigned> &off, std::vector<unsigned> &n_out);
-// ---- wm_small.hip / wm_batch.hip: whole registrations inside one workgroup, many per launch
+float threshold_d2(double max_corr);
+float threshold_d2_strict(double max_corr);
+
+// ---- wm_small.hip: whole registrations inside one workgroup, many per launch
 struct SmallJob {
     const void *src;
     size_t n_src;
@@ -559,13 +605,18 @@ struct SmallResult {
 int small_run(wm_ctx *ctx, const SmallJob *jobs, int n, size_t stride, int mem, const wm_icp_params *p, int with_info,
               double info_max_corr, SmallResult *res, float *kernel_ms);
 void small_fill_stats(const SmallResult &r, float kernel_ms, wm_icp_stats *s);
+
+// ---- wm_batch.hip
+// pcl::VoxelGrid of all the clouds of a batch in one pass (see there)
+int batch_voxel_filter(wm_ctx *ctx, const wm_batch_item *items, const std::vector<int> &idx, size_t stride, int mem, float leaf,
+                       const float4 **filtered, std::vector<unsigned> &off, std::vector<unsigned> &n_out);
 void batch_voxel_release(wm_ctx *ctx);
-void ground_release(wm_ctx *ctx);  // wm_ground.hip
 int batch_match_scaled(wm_ctx *ctx, const wm_batch_item *items, int n_items, size_t stride, int mem,
                        const wm_icp_params *p, float res, int multiscale_steps, int with_info, double *T_out,
                        double *info_out, wm_icp_stats *stats, int *status);
-float threshold_d2(double max_corr);
-float threshold_d2_strict(double max_corr);
+
+// ---- wm_ground.hip
+void ground_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0
@@ -574,18 +625,22 @@ int plane_target_normals(wm_ctx *ctx, int k);  // the target's normals on the co
 int plane_bins_ready(wm_ctx *ctx);
 int launch_plane_stats(wm_ctx *ctx);  // after a search-only launch: the 29 sums into the plane bins
 int launch_plane_solve(wm_ctx *ctx, unsigned long long *pub, int pub_slots, int solve);  // solve == 0: the sums into st->stats only
+
 // ---- wm_gicp.hip
 int source_grid(wm_ctx *ctx);  // the source's own search grid (ctx->src_grid), built over src_orig
 
 // ---- wm_icp.hip
+void init_state(IcpDevState *s, const double *T, const wm_icp_params *p, double prev_mse);  // p == nullptr: a search's state
+int upload_state(wm_ctx *ctx);  // ctx->h_state -> the device
+int bins_ready(wm_ctx *ctx);    // the iteration's bins (wm_bins.hpp) allocated and all zero
 int shard_begin(wm_ctx *ctx, const wm_icp_params *p, double x_lo, double x_hi, double expect, double stripe_finite,
                 bool *brute_out, float *thr_out, double prev_mse0);
 // the iteration loop of one registration (state already uploaded); blk != nullptr: sharded (see wm_icp.hip)
 int icp_run_loop(wm_ctx *ctx, const wm_icp_params *p, bool brute, float thr, struct wm_comm *comm, double *blk,
                  double T_out[16], wm_icp_stats *stats);
-// one correspondence pass with transform T; `predict` lets the search start from the
-// radii in the current keys
-int nn_pass(wm_ctx *ctx, const double T[16], float thr_d2, double max_corr, bool predict, bool slab = false,
-            float slab_lo = 0.f, float slab_hi = 0.f, bool wait = true);
+
+// ---- wm_debug.hip
+// developer (WM_LATE_DEBUG): the resident ICP kernel's stamps after a launch that ran `inside` iterations
+void late_debug_report(wm_ctx *ctx, unsigned late_blocks, int inside, int reason);
 
 }  // namespace wm

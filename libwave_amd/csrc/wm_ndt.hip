@@ -10,7 +10,7 @@
 //   k_ndt_derivs  = computeDerivatives / updateDerivatives / computeHessian: one lane per
 //          source point; pass 1 lists the point's voxels within `res`, pass 2 adds their
 //          terms: score + 6 gradient + the 21 upper-triangle Hessian sums in double,
-//          fixed-order workgroup reduction.  k_sum_fetch (wm_icp.hip) adds the workgroups'
+//          fixed-order workgroup reduction.  k_sum_fetch (wm_fetch.hip) adds the workgroups'
 //          partials; those 28 doubles are the only thing the host sees.
 //   host: Newton step (JacobiSVD solve) + More-Thuente line search
 //          (computeStepLengthMT / trialValueSelectionMT / updateIntervalMT).

@@ -1285,6 +1285,8 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
 #pragma unroll
                 for (int k = 0; k < kStatsLen; ++k) S.st.stats[k] = ex[k];
                 icp_apply_stats(&S.st, ex, (long long) S.tot[kAcc]);
+                // (the rule to leave, on this iteration's unquantised values; the host's rule for the launched
+                // iterations reads the quantised record of an earlier one: CertPolicy::decide, wm_icp_ctl.hpp)
                 unsigned fl = 0;
                 if (S.st.done) fl = kLateDone;
                 else if ((li > 0u || S.st.frac_unsettled < 0.999f) && S.st.frac_unsettled > la.stop_unsettled) fl = kLatePolicy;
@@ -1292,17 +1294,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 else if ((int) (li + 1u) >= la.max_inside) fl = kLateBudget;
                 S.flags = fl;
                 if (la.dbg && li < 64u) la.dbg[li * 4u + 2u] = wall_clock64();  // solved
-                if (la.pub) {  // (the record k_reduce_solve publishes: same layout)
-                    const unsigned f_ch = (unsigned) (fminf(fmaxf(S.st.frac_changed, 0.f), 1.f) * 65535.f + 0.5f);
-                    const unsigned f_un = (unsigned) (fminf(fmaxf(S.st.frac_unsettled, 0.f), 1.f) * 65535.f + 0.5f);
-                    const unsigned long long w = ((unsigned long long) ((unsigned) S.st.iter & 0xFFFFu) << 48) |
-                                                 ((unsigned long long) (__float_as_uint(S.st.step_disp) >> 16) << 32) |
-                                                 ((unsigned long long) f_ch << 16) | (unsigned long long) f_un;
-                    if (S.st.iter >= 1 && S.st.iter <= la.pub_slots)
-                        __hip_atomic_store(la.pub + S.st.iter, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    __hip_atomic_store(la.pub, S.st.done ? (1ull | ((unsigned long long) (unsigned) S.st.iter << 1)) : 0ull,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                publish_step(&S.st, la.pub, la.pub_slots);  // (the record k_reduce_solve publishes)
             }
             __syncthreads();
             reason = S.flags;
