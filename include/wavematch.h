@@ -274,6 +274,14 @@ int wm_debug_bins_sum(const double *x, size_t n, const unsigned *perm, double *o
  * order and the voxel filter are built on above 256k points) on HOST arrays: values_out[i] = the input position of the
  * i-th pair in ascending order of the low `bits` bits of the key (equal keys in input order).  key_bytes: 4 or 8. */
 int wm_debug_sort_pairs(wm_ctx *ctx, const void *keys, int key_bytes, size_t n, unsigned bits, unsigned *values_out);
+/* Developer / tests: the neighbour lists behind wm_gicp_covariances and wm_estimate_normals -- the k nearest points of
+ * every point of the source (which = 0) or the target (which = 1) in its own cloud, the point itself included, found by
+ * the same search on the same grid, along the same query route and from the same first radius (option "knn_r0") as
+ * those two.  idx_out / d2_out: HOST arrays of n_input x k, rows and indices in the caller's order, a row ascending by
+ * (float squared distance, index); -1 / 0 where a list is short and in the row of a non-finite point.  k: 1 ... 32.
+ * WM_NOT_CONVERGED when the cloud has fewer than k finite points, WM_ERR_STATE without both clouds.  Cached covariances,
+ * normals and tuned cell sizes stay as they were. */
+int wm_debug_knn(wm_ctx *ctx, int which, int k, int32_t *idx_out, float *d2_out);
 /* Tuning knobs by name (tests, benchmarks; the defaults are the product's).  Each is also read from the environment
  * when a context is created (mostly WM_TUNE_<NAME>; INTEGRATION.md lists them all).  Among them: "cert_from"
  * (-1: the certificate kernel takes over once an ICP step is small, -2: never, k >= 0: from iteration k of every
@@ -437,7 +445,8 @@ int wm_gicp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, si
 int wm_gicp_eval(wm_ctx *ctx, const wm_gicp_params *p, const double T_pair[16], const double x[6],
                  double *f, double g[6], int *n_pairs);
 /* computeCovariances of both clouds (9 doubles per point, caller order); either output
- * may be NULL (kernel-level parity). */
+ * may be NULL (kernel-level parity).  k: 1 ... 32; WM_NOT_CONVERGED when a cloud has fewer than k finite
+ * points (PCL refuses to align then), nothing written. */
 int wm_gicp_covariances(wm_ctx *ctx, int k, double eps, double *cov_source, double *cov_target);
 
 /* ------------------------------------------------------------------- NDT */

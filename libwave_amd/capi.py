@@ -233,6 +233,7 @@ def lib():
                                         C.POINTER(C.c_int)]
         L.wm_debug_solve_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.wm_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.c_void_p]
+        L.wm_debug_knn.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _fp]
         L.wm_debug_cost_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.wm_debug_phase_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.wm_get_correspondences.argtypes = [C.c_void_p, _ip, _fp, C.c_size_t]
@@ -842,6 +843,19 @@ class Context:
         self._check(lib().wm_debug_sort_pairs(self._h, keys.ctypes.data, keys.dtype.itemsize, keys.shape[0], int(bits),
                                               out.ctypes.data), "wm_debug_sort_pairs")
         return out
+
+    def debug_knn(self, which, k):
+        """wm_debug_knn: the neighbour lists the covariances and normals of the source (which = 0) or the target (1) are
+        made of -> (idx [n, k] int32, d2 [n, k] float32), caller order, ascending by (d2, index); -1 / 0 where a list is
+        short or the point is not finite.  rc = WM_NOT_CONVERGED (fewer than k finite points) raises WmError."""
+        n = self.n_tgt if which == 1 else self.n_src
+        idx = np.full((n, int(k)), -1, np.int32)
+        d2 = np.zeros((n, int(k)), np.float32)
+        rc = self._check(lib().wm_debug_knn(self._h, int(which), int(k), idx.ctypes.data_as(_ip), d2.ctypes.data_as(_fp)),
+                         "wm_debug_knn")
+        if rc != WM_OK:
+            raise WmError("wm_debug_knn: %s" % lib().wm_strerror(rc).decode())
+        return idx, d2
 
     def solve_cycles(self):
         buf = (C.c_uint64 * 8)()

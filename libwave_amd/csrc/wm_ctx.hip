@@ -192,8 +192,9 @@ const char *wm_last_error(const wm_ctx *ctx) { return ctx ? ctx->last_error.c_st
 //   kOpenLo    the range is (lo, hi]
 //   kFlag      any non-zero value means 1 -- except the top of the range, which is kept (gicp_served's 2)
 //   kNdtModel  the NDT voxel model depends on it and is rebuilt
+//   kOrZero    0 is accepted besides the range: back to the library's own choice
 namespace {
-enum : unsigned { kOpenLo = 1u, kFlag = 2u, kNdtModel = 4u };
+enum : unsigned { kOpenLo = 1u, kFlag = 2u, kNdtModel = 4u, kOrZero = 8u };
 struct Option {
     const char *name, *env;
     int wm_ctx::*i;
@@ -228,7 +229,7 @@ const Option kOptions[] = {
     {"gicp_served", "WM_TUNE_GICP_SERVED", &wm_ctx::tune_gicp_served, nullptr, kIntMin, 2, kFlag},
     {"gicp_serve_test_stall_ms", "WM_TUNE_GICP_SERVE_TEST_STALL_MS", &wm_ctx::gicp_serve_test_stall_ms, nullptr, kIntMin, kIntMax, 0},
     {"gicp_blocks", "WM_TUNE_GICP_BLOCKS", &wm_ctx::tune_gicp_blocks, nullptr, 1, 4096, 0},
-    {"knn_r0", "WM_TUNE_KNN_R0", nullptr, &wm_ctx::tune_knn_r0, 0.25, 8, 0},
+    {"knn_r0", "WM_TUNE_KNN_R0", nullptr, &wm_ctx::tune_knn_r0, 0.25, 8, kOrZero},
     {"gicp_profile", "WM_GICP_PROFILE", &wm_ctx::gicp_profile, nullptr, kIntMin, kIntMax, kFlag},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
@@ -243,7 +244,7 @@ const Option kOptions[] = {
 
 int apply_option(wm_ctx *ctx, const Option &o, double v) {
     if ((o.flags & kFlag) && v != o.hi) v = v != 0 ? 1 : 0;
-    if (!(v >= o.lo && v <= o.hi) || ((o.flags & kOpenLo) && v == o.lo)) return WM_ERR_ARG;
+    if ((!(v >= o.lo && v <= o.hi) || ((o.flags & kOpenLo) && v == o.lo)) && !((o.flags & kOrZero) && v == 0)) return WM_ERR_ARG;
     if (o.i) ctx->*o.i = (int) v;
     else ctx->*o.f = (float) v;
     if (o.flags & kNdtModel) ctx->ndt_built = false;

@@ -893,6 +893,51 @@ static int launch_cov_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n
     return launch_cov<32>(ctx, g, q, n, orig, k, eps, out, by_w);
 }
 
+// developer / tests (wm_debug_knn): the neighbour lists themselves, as knn_search<K> hands them to k_gicp_cov and
+// k_normals -- same workgroup shape, same first radius, same K ladder; row `slot` of the outputs (k entries, preset to
+// -1 / 0 by the host: what a short list and a non-finite point's row keep)
+template <int K>
+__global__ void __launch_bounds__(kCovBlock) __attribute__((amdgpu_waves_per_eu(K <= 10 ? 6 : (K <= 12 ? 5 : 1))))
+    k_debug_knn(GridDev g, const float4 *__restrict__ qpts, unsigned n, unsigned n_out, int k, int by_w, float r0_cells,
+                int *__restrict__ idx_out, float *__restrict__ d2_out) {
+    __shared__ uint2 s_runs[kKnnRows * kCovBlock];
+    const unsigned i = blockIdx.x * kCovBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = qpts[i];
+    const unsigned slot = (by_w & 1) ? __float_as_uint(q.w) : i;
+    if (slot >= n_out || !(q.x == q.x)) return;
+    unsigned long long best[K];
+    knn_search<K>(g, q.x, q.y, q.z, k, r0_cells, best, s_runs, threadIdx.x, kCovBlock);
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j < k && best[j] != ~0ull) {
+            idx_out[(size_t) slot * k + j] = (int) (unsigned) best[j];
+            d2_out[(size_t) slot * k + j] = __uint_as_float((unsigned) (best[j] >> 32));
+        }
+}
+
+template <int K>
+static int launch_debug_knn(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, size_t n_out, int k, int by_w, int *idx,
+                            float *d2) {
+    if (n == 0) return WM_OK;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_debug_knn<K>), dim3((unsigned) ((n + kCovBlock - 1) / kCovBlock)), dim3(kCovBlock), 0,
+                       ctx->stream, g, q, (unsigned) n, (unsigned) n_out, k, by_w,
+                       ctx->tune_knn_r0 > 0 ? ctx->tune_knn_r0 : (k <= 12 ? 1.0f : 1.5f), idx, d2);
+    WM_HIP(ctx, hipGetLastError());
+    return WM_OK;
+}
+
+static int launch_debug_knn_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, size_t n_out, int k, int by_w, int *idx,
+                              float *d2) {
+    if (k <= 8) return launch_debug_knn<8>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    if (k <= 10) return launch_debug_knn<10>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    if (k <= 12) return launch_debug_knn<12>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    if (k <= 16) return launch_debug_knn<16>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    if (k <= 20) return launch_debug_knn<20>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    if (k <= 24) return launch_debug_knn<24>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    return launch_debug_knn<32>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+}
+
 // the source's own grid (the target's is the level-0 search grid): what the k-NN of its covariances and normals scans
 int source_grid(wm_ctx *ctx) {
     double occ = 0, vol = 1;
@@ -1012,6 +1057,50 @@ int wm_gicp_covariances(wm_ctx *ctx, int k, double eps, double *cov_source, doub
         }
     }
     return WM_OK;
+}
+
+int wm_debug_knn(wm_ctx *ctx, int which, int k, int32_t *idx_out, float *d2_out) {
+    if (!ctx || (which != 0 && which != 1) || k < 1 || k > 32 || !idx_out || !d2_out) return WM_ERR_ARG;
+    if (ctx->n_src_input == 0 || ctx->n_tgt_input == 0) return WM_ERR_STATE;
+    WM_HIP(ctx, hipSetDevice(ctx->device));
+    WM_TRY(finalize_clouds(ctx));
+    if ((size_t) k > (which == 1 ? ctx->n_tgt : ctx->n_src)) return WM_NOT_CONVERGED;
+    const size_t n_out = which == 1 ? ctx->n_tgt_input : ctx->n_src_input;
+    DevBuf d_idx, d_d2;  // (the call's own: nothing cached on the context is touched)
+    hipError_t e = d_idx.reserve(n_out * k * sizeof(int));
+    if (e == hipSuccess) e = d_d2.reserve(n_out * k * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(d_idx.p, 0xFF, n_out * k * sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_d2.p, 0, n_out * k * sizeof(float), ctx->stream);
+    int rc = WM_OK;
+    if (e == hipSuccess) {
+        if (which == 1) {
+            // the target: the level-0 search grid, queries in its own order unless a point is not finite
+            if (!ctx->levels[0].built) rc = ensure_levels(ctx, -1.0);
+            const GridDev &g = ctx->levels[0].d;
+            if (rc == WM_OK)
+                rc = ctx->n_tgt == ctx->n_tgt_input
+                         ? launch_debug_knn_k(ctx, g, g.pts, ctx->n_tgt, n_out, k, 1, d_idx.as<int>(), d_d2.as<float>())
+                         : launch_debug_knn_k(ctx, g, ctx->tgt_orig.as<float4>(), n_out, n_out, k, 0, d_idx.as<int>(), d_d2.as<float>());
+        } else {
+            // the source: its own grid, built as compute_covariances builds it (the cell size remembered for the next
+            // source stays what it was)
+            const double h = ctx->tuned_src_h, vol = ctx->tuned_src_vol;
+            const unsigned uses = ctx->tuned_src_uses;
+            const size_t n = ctx->tuned_src_n;
+            rc = source_grid(ctx);
+            ctx->tuned_src_h = h, ctx->tuned_src_vol = vol, ctx->tuned_src_uses = uses, ctx->tuned_src_n = n;
+            if (rc == WM_OK)
+                rc = launch_debug_knn_k(ctx, ctx->src_grid.d, ctx->src_sorted.as<float4>(), ctx->n_src, n_out, k, 1, d_idx.as<int>(),
+                                        d_d2.as<float>());
+        }
+    }
+    if (e == hipSuccess && rc == WM_OK) rc = copy_to_caller(ctx, idx_out, d_idx.p, n_out * k * sizeof(int));
+    if (e == hipSuccess && rc == WM_OK) rc = copy_to_caller(ctx, d2_out, d_d2.p, n_out * k * sizeof(float));
+    (void) hipStreamSynchronize(ctx->stream);  // (nothing may still be writing what is freed next)
+    d_idx.release();
+    d_d2.release();
+    WM_HIP(ctx, e);
+    return rc;
 }
 
 int wm_gicp_align(wm_ctx *ctx, const wm_gicp_params *prm, double T_out[16], wm_gicp_stats *stats) {

@@ -49,15 +49,19 @@ def knn(xyz, k, chunk=256):
     return idx, d2o
 
 
-def normals(xyz, k=DEFAULT_K, nbrs=None):
+def normals(xyz, k=DEFAULT_K, nbrs=None, origin=None):
     """-> dict(normal [n, 3], curvature [n], eig [n, 3] ascending, gap [n] = (l1 - l0) / l2, tie [n] = the k-th and
-    (k + 1)-th neighbour distances tie in float, valid [n])."""
+    (k + 1)-th neighbour distances tie in float, valid [n]).  nbrs: (idx, d2) of k + 1 neighbours per point from elsewhere
+    (-1: none).  origin: subtracted from the coordinates, in float64, before the covariance is formed -- for a cloud far
+    from zero, whose covariance about raw coordinates loses (offset^2 x 2^-52) / spread^2 to cancellation; exact when the
+    origin is a whole number.  The flip still looks at the true coordinates."""
     xyz = np.ascontiguousarray(xyz, np.float32)
     n = len(xyz)
     idx, d2 = nbrs if nbrs is not None else knn(xyz, k)
     valid = idx[:, k - 1] >= 0
     P = xyz.astype(np.float64)
-    nb = P[np.where(idx[:, :k] >= 0, idx[:, :k], 0)]  # [n, k, 3]
+    Q = P if origin is None else P - np.asarray(origin, np.float64)
+    nb = Q[np.where(idx[:, :k] >= 0, idx[:, :k], 0)]  # [n, k, 3]
     mean = nb.mean(1, keepdims=True)
     d = nb - mean
     cov = np.einsum("nka,nkb->nab", d, d) / k
@@ -73,6 +77,39 @@ def normals(xyz, k=DEFAULT_K, nbrs=None):
     gap = np.where(ok, (w[:, 1] - w[:, 0]) / np.where(w[:, 2] > 0, w[:, 2], 1.0), 0.0)
     tie = (idx.shape[1] > k) & (idx[:, k] >= 0) & (d2[:, k - 1] == d2[:, k])
     return dict(normal=nrm, curvature=curv, eig=w, gap=gap, tie=tie, valid=ok)
+
+
+def angle(a, b):
+    """angle between the LINES of two unit vectors (sign aside), well conditioned near 0"""
+    return np.arcsin(np.minimum(1.0, np.linalg.norm(np.cross(a, b), axis=1)))
+
+
+def check_normals(got, cloud, k, what, ref=None, cap=0.03):
+    """The device's (nx, ny, nz, curvature) rows against the reference's (`ref`: normals(cloud, k) unless given): unit
+    length, 1e-6 rad, 1e-6 in curvature, turned towards the origin -- on every point but those whose normal the data
+    does not determine (eigen-gap < 1e-3, or a float tie at the k-th neighbour), which may be `cap` of the cloud at
+    the most.  -> (largest angle, largest curvature difference)."""
+    if ref is None:
+        ref = normals(cloud, k)
+    out = (ref["gap"] < 1e-3) | ref["tie"]
+    share = out.mean()
+    print("%s: left out %.3f %%" % (what, 100 * share))
+    assert share <= cap, (what, share)
+    use = ~out & ref["valid"]
+    g = got[use, :3].astype(np.float64)
+    assert np.abs(np.linalg.norm(g, axis=1) - 1.0).max() < 1e-6
+    ang = angle(g, ref["normal"][use])
+    curv = np.abs(got[use, 3] - ref["curvature"][use])
+    print("%s: max angle %.3e rad, max curvature diff %.3e" % (what, ang.max(), curv.max()))
+    assert ang.max() <= 1e-6, (what, ang.max())
+    assert curv.max() <= 1e-6, (what, curv.max())
+    p = cloud[use].astype(np.float64)
+    ndotp = np.einsum("na,na->n", g, p)
+    rounding = 1e-6 * np.linalg.norm(p, axis=1)
+    assert (ndotp <= rounding).all(), what                      # n . p <= 0: towards the origin
+    same = np.einsum("na,na->n", g, ref["normal"][use]) > 0
+    assert (same | (np.abs(ndotp) <= rounding)).all(), what
+    return ang.max(), curv.max()
 
 
 # ------------------------------------------------------------------ sums and step

@@ -40,35 +40,10 @@ def _ref_normals(name, tgt):
     return _NORMALS[name]
 
 
-def _angle(a, b):
-    """angle between the LINES of two unit vectors (sign aside), well conditioned near 0"""
-    return np.arcsin(np.minimum(1.0, np.linalg.norm(np.cross(a, b), axis=1)))
+_check_normals = PR.check_normals  # (shared with tests/test_knn_stress_gpu.py)
 
 
 # ------------------------------------------------------------------ 1. normals
-def _check_normals(got, cloud, k, what):
-    ref = PR.normals(cloud, k)
-    out = (ref["gap"] < 1e-3) | ref["tie"]
-    share = out.mean()
-    print("%s: left out %.3f %%" % (what, 100 * share))
-    assert share <= 0.03, (what, share)
-    use = ~out & ref["valid"]
-    g = got[use, :3].astype(np.float64)
-    assert np.abs(np.linalg.norm(g, axis=1) - 1.0).max() < 1e-6
-    ang = _angle(g, ref["normal"][use])
-    curv = np.abs(got[use, 3] - ref["curvature"][use])
-    print("%s: max angle %.3e rad, max curvature diff %.3e" % (what, ang.max(), curv.max()))
-    assert ang.max() <= 1e-6, (what, ang.max())
-    assert curv.max() <= 1e-6, (what, curv.max())
-    p = cloud[use].astype(np.float64)
-    ndotp = np.einsum("na,na->n", g, p)
-    rounding = 1e-6 * np.linalg.norm(p, axis=1)
-    assert (ndotp <= rounding).all(), what                      # n . p <= 0: towards the origin
-    same = np.einsum("na,na->n", g, ref["normal"][use]) > 0
-    assert (same | (np.abs(ndotp) <= rounding)).all(), what
-    return ang.max(), curv.max()
-
-
 @pytest.mark.parametrize("name", ["uniform", "rings", "testscan"])
 def test_normals_against_the_reference(wm, ctx, oracle, testscan, name):
     import torch
