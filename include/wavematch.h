@@ -203,8 +203,10 @@ int wm_icp_match(wm_ctx *ctx, const void *ref, size_t n_ref, const void *target,
  *             one pass of device-wide kernels, the cloud number above the leaf index in one sort key --
  *             per scale (leaf = 2^i res, i = multiscale_steps .. 0; icp.cpp:77-104) or once
  *             (multiscale_steps == 0; icp.cpp:105-122); an item that fails at a scale stops there, as
- *             match() does.  Items whose filtered target is still too large, or whose leaf lattice
- *             overflows int32, are registered by wm_icp_match inside the call.
+ *             match() does.  Items whose filtered target is still too large, or whose leaf lattice is
+ *             beyond the batched filter (PCL's size rule fires: the product of the truncated extents
+ *             overflows int32 and the cloud stays unfiltered; or the rule passes while the lattice
+ *             itself has 2^32 cells or more), are registered by wm_icp_match inside the call.
  * Results per item k: status[k] (what wm_icp_match would have returned), T_out + 16 k (written
  * when status[k] == WM_OK), info_out + 36 k (with_info; written whenever an align of the item ran),
  * stats[k] (of the item's last align).  T_out, info_out, stats may be NULL.  The call returns WM_OK
@@ -228,13 +230,14 @@ int wm_icp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
  * with res > 0, exposed): cloud 2 k = items[k].src, 2 k + 1 = items[k].target; their centroids, back
  * to back in that order, as packed xyz floats in host memory out_xyz (capacity cap_points points),
  * their counts in n_out[2 n_items].  Same results, bit for bit, as wm_voxel_downsample cloud by cloud
- * (a leaf lattice beyond int32 is WM_ERR_ARG here). */
+ * (a cloud for which PCL's size rule fires -- wm_voxel_downsample returns it unfiltered -- or whose
+ * lattice has 2^32 cells or more is WM_ERR_ARG here). */
 int wm_voxel_downsample_batch(wm_ctx *ctx, const wm_batch_item *items, int n_items, size_t stride_bytes,
                               int mem, float leaf, float *out_xyz, size_t cap_points, size_t *n_out);
 
 /* pcl::VoxelGrid<PointXYZ>::filter on device (icp.cpp:81-90,106-113; gicp.cpp:39-40,
- * 49-50): float centroid per occupied leaf, ascending leaf index; `out` must hold
- * `cap` points of `out_stride` bytes. */
+ * 49-50): float centroid per occupied leaf, ascending leaf index (PCL's `unsigned int` index:
+ * mod 2^32 where the lattice has more cells); `out` must hold `cap` points of `out_stride` bytes. */
 int wm_voxel_downsample(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
                         float leaf, void *out, size_t out_stride, int out_mem, size_t cap,
                         size_t *n_out);

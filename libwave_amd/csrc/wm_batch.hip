@@ -11,8 +11,9 @@
 //     carrying its own stopping-criteria state, running transform and fail-fast status.
 // A pair is registered one scale at a time together with all the others; pairs that failed stop
 // (icp.cpp:96-98).  Pairs whose filtered target does not fit the resident kernel (more than 65 535
-// points), or whose leaf grid overflows int32 (PCL then returns the cloud unfiltered), are handed to
-// wm_icp_match one by one.
+// points), or whose leaf grid is beyond this pass -- PCL's size rule fires and the cloud comes back
+// unfiltered, or the rule passes while the lattice has 2^32 cells or more (wm_voxel.hip) --, are handed
+// to wm_icp_match one by one.
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
@@ -43,9 +44,9 @@ struct VbBox {  // per cloud, found once (the same cloud is filtered at every sc
 struct VbLeaf {  // per cloud and leaf size
     float inv;
     int mb[3];
-    int dx, dxy;
+    unsigned dx, dxy;
     unsigned invalid;  // number of leaves = the key of dropped points
-    int overflow;      // dx * dy * dz does not fit int32: PCL returns the input unfiltered
+    int overflow;      // PCL's size rule fires (it returns the input unfiltered), or the lattice has >= 2^32 cells
 };
 
 // the cloud a position of the concatenated arrays belongs to (clouds are laid out back to back)
@@ -135,14 +136,17 @@ __global__ void __launch_bounds__(kBlock)
         if (ex * ey * ez > 2147483647ll) {
             l.overflow = 1;
         } else {
-            int db[3];
+            unsigned db[3];
             for (int d = 0; d < 3; ++d) {
                 l.mb[d] = (int) floorf(__fmul_rn(b.lo[d], l.inv));
-                db[d] = (int) floorf(__fmul_rn(b.hi[d], l.inv)) - l.mb[d] + 1;
+                db[d] = (unsigned) ((int) floorf(__fmul_rn(b.hi[d], l.inv)) - l.mb[d] + 1);
             }
+            // (the rule looks at truncated extents: the lattice can have one cell more per axis, wm_voxel.hip)
+            const unsigned long long cells = (unsigned long long) db[0] * db[1] * db[2];
             l.dx = db[0];
             l.dxy = db[0] * db[1];
-            l.invalid = (unsigned) ((long long) db[0] * db[1] * db[2]);
+            if (cells > 0xFFFFFFFFull) l.overflow = 1;  // keys wrap mod 2^32: the one-cloud path's 64-bit sort
+            else l.invalid = (unsigned) cells;
         }
     }
     out[c] = l;
@@ -164,7 +168,7 @@ __global__ void __launch_bounds__(kBlock)
         const int i0 = (int) (floorf(__fmul_rn(p.x, l.inv)) - (float) l.mb[0]);
         const int i1 = (int) (floorf(__fmul_rn(p.y, l.inv)) - (float) l.mb[1]);
         const int i2 = (int) (floorf(__fmul_rn(p.z, l.inv)) - (float) l.mb[2]);
-        k = (unsigned) (i0 + i1 * l.dx + i2 * l.dxy);
+        k = (unsigned) i0 + (unsigned) i1 * l.dx + (unsigned) i2 * l.dxy;
     }
     key[g] = ((unsigned long long) c << shift) | k;  // (shift = bits of the batch's largest leaf count: fewer radix passes)
     perm[g] = g;
@@ -370,7 +374,7 @@ struct VoxelBatch {
     VbXform *d_xf() const { return reinterpret_cast<VbXform *>(dt + o_xf); }
 
     // pcl::VoxelGrid of every cloud whose h_skip entry is 0: centroids into `filtered` at the cloud's
-    // offset, their number into n_out (0xFFFFFFFF: the leaf lattice overflows int32)
+    // offset, their number into n_out (0xFFFFFFFF: VbLeaf::overflow)
     int filter(float leaf) {
         const unsigned blocks = (unsigned) ((total + kBlock - 1) / kBlock), cblocks = (n_clouds + kBlock - 1) / kBlock;
         // the widest leaf count of the batch at this scale (k_vb_leaf's arithmetic) -> bits of the key's leaf part
@@ -386,7 +390,7 @@ struct VoxelBatch {
                     const long long m = (long long) floorf(b.lo[d] * inv), M = (long long) floorf(b.hi[d] * inv);
                     cells *= (unsigned long long) (M - m + 1);
                 }
-                if (cells <= 2147483647ull && cells > most) most = cells;  // (beyond int32: overflow, key = 0)
+                if (cells <= 0xFFFFFFFFull && cells > most) most = cells;  // (2^32 and beyond: overflow, key = 0)
             }
             while (shift < 32 && (most >> shift) != 0ull) ++shift;
         }
@@ -546,7 +550,7 @@ static int scaled_sub_batch(wm_ctx *ctx, const wm_batch_item *items, const std::
 
 // pcl::VoxelGrid of every cloud of `idx`'s items (cloud 2 j = the ref of item idx[j], 2 j + 1 = its target) in one
 // pass: *filtered + off[c] = cloud c's centroids (float4, device memory of this context, valid until the next batched
-// filter), n_out[c] their number (0xFFFFFFFF: the leaf lattice overflows int32 -- PCL returns that cloud unfiltered).
+// filter), n_out[c] their number (0xFFFFFFFF: VbLeaf::overflow -- the one-cloud path's business).
 int batch_voxel_filter(wm_ctx *ctx, const wm_batch_item *items, const std::vector<int> &idx, size_t stride, int mem, float leaf,
                        const float4 **filtered, std::vector<unsigned> &off, std::vector<unsigned> &n_out) {
     off.assign(2 * idx.size(), 0u);
@@ -589,7 +593,7 @@ int batch_match_scaled(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
             pts += need;
         }
     }
-    for (int k : one_by_one) {  // (leaf lattice beyond int32, or a filtered target beyond the resident kernel)
+    for (int k : one_by_one) {  // (VbLeaf::overflow, or a filtered target beyond the resident kernel)
         // a pair of its own starts with fresh stopping criteria, but its SCALES carry the last MSE from one
         // align to the next, as the batched path and the reference's one PCL object do
         wm_icp_params q = *p;
@@ -640,7 +644,7 @@ int wm_voxel_downsample_batch(wm_ctx *ctx, const wm_batch_item *items, int n_ite
     WM_TRY(vb.filter(leaf));
     size_t need = 0;
     for (unsigned c = 0; c < vb.n_clouds; ++c) {
-        if (vb.n_out[c] == 0xFFFFFFFFu) return WM_ERR_ARG;  // leaf lattice beyond int32: wm_voxel_downsample returns the input
+        if (vb.n_out[c] == 0xFFFFFFFFu) return WM_ERR_ARG;  // VbLeaf::overflow: wm_voxel_downsample's business
         n_out[c] = vb.n_out[c];
         need += vb.n_out[c];
     }

@@ -7,7 +7,9 @@
 // ijk = floor(p * (1/leaf)) - floor(min * (1/leaf)) in float, linear index
 // i + j*dx + k*dx*dy, one float centroid (sequential float sum, ascending point
 // index) per occupied leaf, output in ascending leaf-index order; non-finite points
-// are skipped; if dx*dy*dz overflows int32 the input is returned unfiltered.
+// are skipped; if the product of the truncated extents (int64) ((max - min) / leaf) + 1 overflows int32
+// the input is returned unfiltered (PCL's rule).  The lattice's own cell count can still reach 2^32 and
+// beyond: the leaf index is PCL's `unsigned int`, arithmetic mod 2^32 (voxel_downsample_dev).
 // The sort by leaf index is rocPRIM's stable radix sort (a plain library sort);
 // everything else is hand-written.
 #include <cstring>
@@ -19,40 +21,42 @@
 
 namespace wm {
 
+// K = unsigned: the leaf index itself, `invalid` = the number of leaves.  K = unsigned long long (a lattice of 2^32
+// cells or more, below): the leaf index mod 2^32 -- PCL's `unsigned int` key --, `invalid` = 2^32.
+template <class K>
 __global__ void __launch_bounds__(kBlock)
     k_vg_index(const float4 *__restrict__ in, unsigned n, float inv, int mbx, int mby, int mbz,
-               int dx, int dxy, unsigned invalid, unsigned *__restrict__ idx,
-               unsigned *__restrict__ perm) {
+               unsigned dx, unsigned dxy, K invalid, K *__restrict__ idx, unsigned *__restrict__ perm) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const float4 p = in[i];
-    unsigned key = invalid;  // one past the last leaf: invalid points sort to the end
+    K key = invalid;  // one past the last leaf: invalid points sort to the end
     if (p.x == p.x) {
         const int i0 = (int) (floorf(__fmul_rn(p.x, inv)) - (float) mbx);
         const int i1 = (int) (floorf(__fmul_rn(p.y, inv)) - (float) mby);
         const int i2 = (int) (floorf(__fmul_rn(p.z, inv)) - (float) mbz);
-        key = (unsigned) (i0 + i1 * dx + i2 * dxy);
+        key = (K) ((unsigned) i0 + (unsigned) i1 * dx + (unsigned) i2 * dxy);  // (unsigned: wraps mod 2^32, defined)
     }
     idx[i] = key;
     perm[i] = i;
 }
 
 // head flag per sorted position (1 where a new leaf starts); invalid tail gets 0
+template <class K>
 __global__ void __launch_bounds__(kBlock)
-    k_vg_flags(const unsigned *__restrict__ idx_sorted, unsigned n, unsigned invalid,
-               unsigned *__restrict__ flags) {
+    k_vg_flags(const K *__restrict__ idx_sorted, unsigned n, K invalid, unsigned *__restrict__ flags) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const unsigned k = idx_sorted[i];
+    const K k = idx_sorted[i];
     flags[i] = (k != invalid && (i == 0 || idx_sorted[i - 1] != k)) ? 1u : 0u;
 }
 
 // heads[slot] = first sorted position of leaf `slot`; heads[n_leaves] = one past the last valid
 // point (seg[n] = n_leaves, the scan's total)
+template <class K>
 __global__ void __launch_bounds__(kBlock)
-    k_vg_heads(const unsigned *__restrict__ idx_sorted, const unsigned *__restrict__ flags,
-               const unsigned *__restrict__ seg, unsigned n, unsigned invalid,
-               unsigned *__restrict__ heads) {
+    k_vg_heads(const K *__restrict__ idx_sorted, const unsigned *__restrict__ flags,
+               const unsigned *__restrict__ seg, unsigned n, K invalid, unsigned *__restrict__ heads) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     if (flags[i]) heads[seg[i]] = i;
@@ -144,6 +148,51 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// The filter proper, once the lattice is known: sort by key, leaf heads, centroids.  K as k_vg_index's; the sort looks
+// at the low `bits` bits of the key (those of `invalid`).
+template <class K>
+static int vg_filter(wm_ctx *ctx, const float4 *in, size_t n, size_t valid, float inv, const int mb[3], unsigned dx,
+                     unsigned dxy, K invalid, int bits, float4 *out, size_t *n_out) {
+    const unsigned blocks = (unsigned) ((n + kBlock - 1) / kBlock);
+    WM_HIP(ctx, ctx->vg_idx.reserve(n * sizeof(K)));
+    WM_HIP(ctx, ctx->vg_idx2.reserve(n * sizeof(K)));
+    WM_HIP(ctx, ctx->vg_perm.reserve((n + 1) * 4));  // after the sort: the leaves' head positions (+ end)
+    WM_HIP(ctx, ctx->vg_perm2.reserve(n * 4));
+    WM_HIP(ctx, ctx->vg_seg.reserve((n + 1) * 4));
+    K *idx = ctx->vg_idx.as<K>(), *idx2 = ctx->vg_idx2.as<K>();
+    unsigned *perm = ctx->vg_perm.as<unsigned>(), *perm2 = ctx->vg_perm2.as<unsigned>();
+    unsigned *seg = ctx->vg_seg.as<unsigned>();
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vg_index<K>), dim3(blocks), dim3(kBlock), 0, ctx->stream, in, (unsigned) n,
+                       inv, mb[0], mb[1], mb[2], dx, dxy, invalid, idx, perm);
+    size_t tmp_bytes = 0;
+    WM_HIP(ctx, sort_pairs_low_bits(nullptr, tmp_bytes, idx, idx2, perm, perm2, n, bits, ctx->stream,
+                                    (size_t) ctx->tune_radix_min));
+    WM_HIP(ctx, ctx->vg_tmp.reserve(tmp_bytes));
+    WM_HIP(ctx, sort_pairs_low_bits(ctx->vg_tmp.p, tmp_bytes, idx, idx2, perm, perm2, n, bits, ctx->stream,
+                                    (size_t) ctx->tune_radix_min));
+    // head flags -> exclusive scan -> output slot per leaf; total = number of leaves
+    unsigned *flags = ctx->vg_idx.as<unsigned>();  // the sort's input keys are dead by now
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vg_flags<K>), dim3(blocks), dim3(kBlock), 0, ctx->stream, (const K *) idx2,
+                       (unsigned) n, invalid, flags);
+    WM_TRY(exclusive_scan(ctx, flags, n, seg));
+    unsigned *heads = perm;  // the sort's input permutation is dead by now
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_vg_heads<K>), dim3(blocks), dim3(kBlock), 0, ctx->stream, (const K *) idx2,
+                       (const unsigned *) flags, (const unsigned *) seg, (unsigned) n, invalid, heads);
+    // two launches, one of which leaves at once: which one is decided on the device from the
+    // average leaf size (the leaf count is not on the host yet, and fetching it first would cost
+    // more than the idle launch)
+    hipLaunchKernelGGL(k_vg_centroid, dim3(blocks), dim3(kBlock), 0, ctx->stream, in, perm2, heads,
+                       seg + n, (unsigned) valid, out);
+    hipLaunchKernelGGL(k_vg_centroid_wave, dim3(2048), dim3(kBlock), 0, ctx->stream, in, perm2, heads,
+                       seg + n, (unsigned) valid, out);
+    WM_HIP(ctx, hipGetLastError());
+    unsigned *h_total = (unsigned *) pinned_scratch(ctx, 0);
+    if (!h_total) return WM_ERR_HIP;
+    WM_TRY(fast_fetch(ctx, h_total, seg + n, 4));
+    *n_out = *h_total;
+    return WM_OK;
+}
+
 int voxel_downsample_dev(wm_ctx *ctx, const float4 *in, size_t n, float leaf, float4 *out,
                          size_t *n_out, const VgKnown *known) {
     *n_out = 0;
@@ -162,62 +211,34 @@ int voxel_downsample_dev(wm_ctx *ctx, const float4 *in, size_t n, float leaf, fl
     const int64_t ex = (int64_t) ((bb.hi[0] - bb.lo[0]) * inv) + 1;
     const int64_t ey = (int64_t) ((bb.hi[1] - bb.lo[1]) * inv) + 1;
     const int64_t ez = (int64_t) ((bb.hi[2] - bb.lo[2]) * inv) + 1;
-    const unsigned blocks = (unsigned) ((n + kBlock - 1) / kBlock);
     if (ex * ey * ez > (int64_t) INT32_MAX) {
         // PCL: "Leaf size is too small for the input dataset" -> output = input
-        hipLaunchKernelGGL(k_copy_valid, dim3(blocks), dim3(kBlock), 0, ctx->stream, in,
+        hipLaunchKernelGGL(k_copy_valid, dim3((unsigned) ((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, in,
                            (unsigned) n, out);
         WM_HIP(ctx, hipGetLastError());
         *n_out = n;
         return WM_OK;
     }
-    int mb[3], db[3];
+    // PCL's rule above looks at the TRUNCATED extents; the lattice itself spans floor(max) - floor(min) + 1 cells
+    // per axis, which can be one more: a cloud thinner than a leaf that straddles a leaf boundary passes the rule
+    // with up to ~2^33 cells.  PCL's keys are `unsigned int`: the leaf index mod 2^32, formed here without signed
+    // overflow.
+    int mb[3];
+    unsigned db[3];
     for (int d = 0; d < 3; ++d) {
         mb[d] = (int) floorf(bb.lo[d] * inv);
-        db[d] = (int) floorf(bb.hi[d] * inv) - mb[d] + 1;
+        db[d] = (unsigned) ((int) floorf(bb.hi[d] * inv) - mb[d] + 1);
     }
-    WM_HIP(ctx, ctx->vg_idx.reserve(n * 4));
-    WM_HIP(ctx, ctx->vg_idx2.reserve(n * 4));
-    WM_HIP(ctx, ctx->vg_perm.reserve((n + 1) * 4));  // after the sort: the leaves' head positions (+ end)
-    WM_HIP(ctx, ctx->vg_perm2.reserve(n * 4));
-    WM_HIP(ctx, ctx->vg_seg.reserve((n + 1) * 4));
-    unsigned *idx = ctx->vg_idx.as<unsigned>(), *idx2 = ctx->vg_idx2.as<unsigned>();
-    unsigned *perm = ctx->vg_perm.as<unsigned>(), *perm2 = ctx->vg_perm2.as<unsigned>();
-    unsigned *seg = ctx->vg_seg.as<unsigned>();
-    // leaf indices run 0 .. total-1; `total` itself marks dropped points, so the sort only
-    // needs the bits of `total` (coarse leaves: 2-3 radix passes instead of 4)
-    const unsigned invalid = (unsigned) ((int64_t) db[0] * db[1] * db[2]);
+    const unsigned dx = db[0], dxy = db[0] * db[1];
+    const unsigned long long cells = (unsigned long long) db[0] * db[1] * db[2];
+    if (cells > 0xFFFFFFFFull)  // rare: wrapped keys take any 32-bit value, the dropped points' key is 2^32 (33 bits)
+        return vg_filter<unsigned long long>(ctx, in, n, valid, inv, mb, dx, dxy, 1ull << 32, 33, out, n_out);
+    // leaf indices run 0 .. cells-1; `cells` itself marks dropped points, so the sort only
+    // needs the bits of `cells` (coarse leaves: 2-3 radix passes instead of 4)
+    const unsigned invalid = (unsigned) cells;
     int bits = 1;
     while (bits < 32 && (invalid >> bits) != 0u) ++bits;
-    hipLaunchKernelGGL(k_vg_index, dim3(blocks), dim3(kBlock), 0, ctx->stream, in, (unsigned) n,
-                       inv, mb[0], mb[1], mb[2], db[0], db[0] * db[1], invalid, idx, perm);
-    size_t tmp_bytes = 0;
-    WM_HIP(ctx, sort_pairs_low_bits(nullptr, tmp_bytes, idx, idx2, perm, perm2, n, bits, ctx->stream,
-                                    (size_t) ctx->tune_radix_min));
-    WM_HIP(ctx, ctx->vg_tmp.reserve(tmp_bytes));
-    WM_HIP(ctx, sort_pairs_low_bits(ctx->vg_tmp.p, tmp_bytes, idx, idx2, perm, perm2, n, bits, ctx->stream,
-                                    (size_t) ctx->tune_radix_min));
-    // head flags -> exclusive scan -> output slot per leaf; total = number of leaves
-    hipLaunchKernelGGL(k_vg_flags, dim3(blocks), dim3(kBlock), 0, ctx->stream, idx2, (unsigned) n,
-                       invalid, idx /* reuse as flags */);
-    WM_TRY(exclusive_scan(ctx, idx, n, seg));
-    unsigned *heads = perm;  // the sort's input permutation is dead by now
-    hipLaunchKernelGGL(k_vg_heads, dim3(blocks), dim3(kBlock), 0, ctx->stream, idx2, idx, seg,
-                       (unsigned) n, invalid, heads);
-    // two launches, one of which leaves at once: which one is decided on the device from the
-    // average leaf size (the leaf count is not on the host yet, and fetching it first would cost
-    // more than the idle launch)
-    hipLaunchKernelGGL(k_vg_centroid, dim3(blocks), dim3(kBlock), 0, ctx->stream, in, perm2, heads,
-                       seg + n, (unsigned) valid, out);
-    hipLaunchKernelGGL(k_vg_centroid_wave, dim3(2048), dim3(kBlock), 0, ctx->stream, in, perm2, heads,
-                       seg + n, (unsigned) valid, out);
-    WM_HIP(ctx, hipGetLastError());
-    unsigned *h_total = (unsigned *) pinned_scratch(ctx, 0);
-    if (!h_total) return WM_ERR_HIP;
-    WM_TRY(fast_fetch(ctx, h_total, seg + n, 4));
-    const unsigned total = *h_total;
-    *n_out = total;
-    return WM_OK;
+    return vg_filter<unsigned>(ctx, in, n, valid, inv, mb, dx, dxy, invalid, bits, out, n_out);
 }
 
 // pcl::transformPointCloud(in, out, Eigen::Affine3d): double arithmetic
