@@ -702,6 +702,60 @@ int wm_ground_segment_batch(wm_ctx *ctx, const wm_ground_scan *scans, int n_scan
                             uint8_t *labels_out /* NULL ok */, wm_ground_stats *stats /* NULL ok */,
                             float *kernel_ms /* NULL ok */);
 
+/* ------------------------------------------------------------- outlier removal */
+/* pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval on the device.  The rules are restated from PCL 1.8
+ * (PCL is not linked; tests/outlier_reference.py is the checker):
+ *   both         squared distances are float32, d2 = (dx * dx + dy * dy) + dz * dz with every operation rounded and
+ *                nothing fused; kept indices ascend; negative != 0 returns the outliers instead of the inliers.
+ *   statistical  [PCL-upstream filters/impl/statistical_outlier_removal.hpp]  per finite point its mean_k + 1 nearest
+ *                points of the cloud, ordered by (d2, index), itself included; the first entry (d2 = 0: the point or a
+ *                duplicate) is skipped; s = the sum of sqrt((double) d2) over the other mean_k, in list order, in
+ *                double; the point's mean distance = (float) (s / mean_k).  Over the n finite points, the distances
+ *                widened to double: mean = sum d / n, var = (sum d^2 - (sum d)^2 / n) / (n - 1), stddev = sqrt(var),
+ *                threshold = mean + stddev_mult * stddev.  Outlier iff (double) dist > threshold; a NaN threshold
+ *                removes nothing.  Fewer than mean_k + 1 finite points: WM_NOT_CONVERGED, nothing written.
+ *                mean_k is 1 ... 31 (the k-NN search keeps lists of 32): beyond it WM_ERR_ARG.
+ *   radius       [PCL-upstream filters/impl/radius_outlier_removal.hpp, FLANN's RadiusResultSet]  r2 = (float)
+ *                (radius * radius), the product formed in double; a point's count = the OTHER finite points with
+ *                d2 < r2 (strict); inlier iff count >= min_neighbors (PCL's "k <= min_pts is an outlier" with the
+ *                point itself in k).  radius finite and > 0, min_neighbors >= 0, else WM_ERR_ARG.
+ *   deviation    a non-finite point is nobody's neighbour, enters no statistic, gets WM_OUTLIER_NONE and is returned
+ *                with neither setting of `negative` (PCL keeps such a point, with distance 0): wm_set_source drops
+ *                them the same way. */
+enum { WM_OUTLIER_STATISTICAL = 0, WM_OUTLIER_RADIUS = 1 };
+enum { WM_OUTLIER_NONE = 0, WM_OUTLIER_INLIER = 1, WM_OUTLIER_OUTLIER = 2 };
+typedef struct {
+    int method;          /* WM_OUTLIER_STATISTICAL or WM_OUTLIER_RADIUS */
+    int mean_k;          /* statistical: neighbours per point, 1 ... 31 */
+    double stddev_mult;  /* statistical: threshold = mean + stddev_mult * stddev */
+    double radius;       /* radius: metres, finite and > 0 */
+    int min_neighbors;   /* radius: inlier with at least this many other points inside */
+    int negative;        /* != 0: return the outliers */
+} wm_outlier_params;
+typedef struct {
+    size_t n_finite, n_inliers, n_outliers;
+    double mean, stddev, threshold;  /* statistical; 0 in radius mode */
+    float kernel_ms;                 /* device time from the cloud's packing to the kept list (the grid's two small
+                                        fetches to the host included) */
+} wm_outlier_stats;
+void wm_outlier_default_params(wm_outlier_params *p);  /* PCL's: mean_k 1, stddev_mult 0, radius 0, min_neighbors 1 */
+
+/* One filter pass over n records of `stride_bytes` (x y z first) in `mem`.  indices_out: the kept points' indices,
+ * ascending; *n_out their number; more than `cap`: WM_ERR_ARG with the first `cap` written and *n_out the true count.
+ * `out_mem` says where all four output arrays live.  labels_out (NULL ok): WM_OUTLIER_* per input point.
+ * mean_dist_out (NULL ok, statistical): the mean distance per point, 0 for a non-finite one.  counts_out (NULL ok,
+ * radius): the exact neighbour count per point, -1 for a non-finite one; without it a point's search stops once it
+ * has seen min_neighbors.  Argument errors (a null context, params or n_out, a bad stride, mem or method, parameters
+ * out of range) are found before a device is touched.  n == 0 or a cloud without a finite point: WM_OK, *n_out = 0.
+ * The cloud's grid is built for the call; the workspace is the context's own (grown on demand, freed by
+ * wm_ctx_destroy); a context's registration state (clouds, grids, cached covariances and normals, tuned cell sizes)
+ * is not touched. */
+int wm_outlier_filter(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                      const wm_outlier_params *p, int32_t *indices_out, size_t cap, int out_mem, size_t *n_out,
+                      uint8_t *labels_out /* NULL ok */, float *mean_dist_out /* NULL ok, statistical */,
+                      int32_t *counts_out /* NULL ok, radius; -1 for a non-finite point */,
+                      wm_outlier_stats *stats /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

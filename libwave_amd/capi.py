@@ -112,6 +112,21 @@ class GroundStats(C.Structure):
 WM_GROUND_NONE, WM_GROUND_GROUND, WM_GROUND_OBSTACLE, WM_GROUND_OVERHANGING = 0, 1, 2, 3
 WM_KEEP_GROUND, WM_KEEP_OBSTACLE, WM_KEEP_OVERHANGING = 1, 2, 4
 
+
+class OutlierParams(C.Structure):
+    _fields_ = [("method", C.c_int), ("mean_k", C.c_int), ("stddev_mult", C.c_double), ("radius", C.c_double),
+                ("min_neighbors", C.c_int), ("negative", C.c_int)]
+
+
+class OutlierStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("n_inliers", C.c_size_t), ("n_outliers", C.c_size_t),
+                ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("kernel_ms", C.c_float)]
+
+
+WM_OUTLIER_STATISTICAL, WM_OUTLIER_RADIUS = 0, 1
+WM_OUTLIER_NONE, WM_OUTLIER_INLIER, WM_OUTLIER_OUTLIER = 0, 1, 2
+WM_OUTLIER_MAX_MEAN_K = 31  # the k-NN search keeps lists of 32, the point itself among them
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -251,6 +266,11 @@ def lib():
                                               C.POINTER(GroundParams), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                               C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p,
                                               C.POINTER(GroundStats), C.POINTER(C.c_float)]
+        L.wm_outlier_default_params.argtypes = [C.POINTER(OutlierParams)]
+        L.wm_outlier_default_params.restype = None
+        L.wm_outlier_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(OutlierParams),
+                                        C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(OutlierStats)]
         _LIB = L
     return _LIB
 
@@ -303,6 +323,17 @@ def ground_params(params=None, **kw):
     """wm_ground_params from the defaults (GroundSegmentationParams), a dict of field values and keywords."""
     p = GroundParams()
     lib().wm_ground_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def outlier_params(params=None, **kw):
+    """wm_outlier_params from PCL's defaults (wm_outlier_default_params), a dict of field values and keywords."""
+    p = OutlierParams()
+    lib().wm_outlier_default_params(C.byref(p))
     for k, v in dict(params or {}, **kw).items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -516,6 +547,49 @@ class Context:
                                             C.c_void_p(labels.ctypes.data), C.byref(st)), "wm_ground_segment")
         stats = {k: getattr(st, k) for k, _ in GroundStats._fields_}
         return labels[:n].copy(), idx[:m.value].copy(), stats
+
+    def outlier_filter(self, cloud, params=None, counts=True, **kw):
+        """pcl::StatisticalOutlierRemoval / RadiusOutlierRemoval on the device (wm_outlier_filter) -> dict: rc, indices
+        (the kept points, ascending int32), labels (n,) uint8 WM_OUTLIER_*, mean_dist (n,) float32 (statistical) or
+        counts (n,) int32 (radius; None with counts=False, which lets a point's search stop at min_neighbors), and the
+        fields of wm_outlier_stats.  `cloud`: float32 (n, 3|4) numpy array, or a HIP torch tensor -- then the outputs
+        are written in device memory and come back as tensors.  `params`: an OutlierParams, a dict of its fields, or
+        None (PCL's defaults); keywords override fields.  rc: WM_OK or WM_NOT_CONVERGED (fewer than mean_k + 1 finite
+        points: indices empty, the other arrays None)."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        if isinstance(params, OutlierParams):
+            params = {k: getattr(params, k) for k, _ in OutlierParams._fields_}
+        p = outlier_params(params, **kw)
+        stat = p.method == WM_OUTLIER_STATISTICAL
+        m = C.c_size_t(0)
+        st = OutlierStats()
+        if mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            labels = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+            extra = (torch.zeros(max(n, 1), dtype=torch.float32, device=dev) if stat else
+                     torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev) if counts else None)
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            idx = np.empty(max(n, 1), np.int32)
+            labels = np.zeros(max(n, 1), np.uint8)
+            extra = np.zeros(max(n, 1), np.float32) if stat else np.full(max(n, 1), -1, np.int32) if counts else None
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = self._check(lib().wm_outlier_filter(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), addr(idx), n, mem,
+                                                 C.byref(m), addr(labels), addr(extra) if stat else None,
+                                                 None if stat else addr(extra), C.byref(st)), "wm_outlier_filter")
+        out = dict(rc=rc, indices=idx[:m.value], labels=None, mean_dist=None, counts=None)
+        if rc == WM_OK:
+            out["labels"] = labels[:n]
+            out["mean_dist" if stat else "counts"] = extra[:n] if extra is not None else None
+        out.update({k: getattr(st, k) for k, _ in OutlierStats._fields_})
+        return out
 
     def ground_segment_batch(self, clouds, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING, points=False):
         """The filter for a queue of scans in one device call (wm_ground_segment_batch) -> [(labels, indices,

@@ -231,6 +231,8 @@ const Option kOptions[] = {
     {"gicp_blocks", "WM_TUNE_GICP_BLOCKS", &wm_ctx::tune_gicp_blocks, nullptr, 1, 4096, 0},
     {"knn_r0", "WM_TUNE_KNN_R0", nullptr, &wm_ctx::tune_knn_r0, 0.25, 8, kOrZero},
     {"gicp_profile", "WM_GICP_PROFILE", &wm_ctx::gicp_profile, nullptr, kIntMin, kIntMax, kFlag},
+    // outlier removal (wm_outlier.hip)
+    {"outlier_cell_div", "WM_TUNE_OUTLIER_CELL_DIV", nullptr, &wm_ctx::tune_outlier_cell_div, 0.5, 8, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
     {"ndt_dense", "WM_TUNE_NDT_DENSE", &wm_ctx::tune_ndt_dense, nullptr, kIntMin, kIntMax, 0},
@@ -320,6 +322,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     ctx->ndt_stage.release();
     batch_voxel_release(ctx);
     ground_release(ctx);
+    outlier_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

@@ -293,6 +293,8 @@ struct wm_ctx {
     int tune_gicp_blocks = 256;  // workgroups (= partial rows) of one GICP objective evaluation (double-double sums: 512 / 256 / 128 / 64 -> 6.9 / 6.4 / 7.3 / 9.6 ms per 500k registration)
     float tune_knn_r0 = 0.f;     // first radius of the k-NN (covariance) scan in cells, 0.25 ... 8; 0 = by k (1.0 up to k = 12, else 1.5)
     int gicp_profile = 0;        // HIP events around every objective evaluation (fdf_kernel_ms)
+    // outlier removal (wm_outlier.hip)
+    float tune_outlier_cell_div = 2.f;  // the radius filter's grid cell is at least radius / this (0.5 ... 8)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_ndt_dense = 2;      // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice
@@ -321,6 +323,7 @@ struct wm_ctx {
     wm::PairStage icp_stage, gicp_stage, ndt_stage;  // staging of the batched small registrations (wm_small.hip, wm_gicp_small.hip, wm_ndt_small.hip)
     void *batch_voxel = nullptr;            // wm_batch.hip: buffers of the batched voxel filter
     void *ground = nullptr;                 // wm_ground.hip: the ground filter's workspace (its own, shared with nothing)
+    void *outlier = nullptr;                // wm_outlier.hip: the outlier filters' workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -617,6 +620,9 @@ int batch_match_scaled(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
 
 // ---- wm_ground.hip
 void ground_release(wm_ctx *ctx);
+
+// ---- wm_outlier.hip
+void outlier_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0

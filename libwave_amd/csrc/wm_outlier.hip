@@ -1,0 +1,452 @@
+// wm_outlier.hip -- outlier removal on the device: pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval as one
+// cloud-in / indices-out call (wm_outlier_filter), shaped like wm_ground_segment: the call packs the cloud, builds a
+// cell-sorted grid over it for this call alone, and works in a workspace of its own on the context.
+//
+// The rules (written from PCL 1.8; PCL is not linked, the checker is tests/outlier_reference.py):
+//   [PCL-upstream filters/impl/statistical_outlier_removal.hpp applyFilterIndices]  per point the mean_k + 1 nearest
+//     points of the cloud, itself included; the first entry (d2 = 0: the point or a duplicate of it) is skipped, the
+//     other mean_k distances sqrt((double) d2) are added in list order in double, and the point's mean distance is
+//     (float) (sum / mean_k).  Over the n finite points, the float distances widened to double:
+//       mean = sum d / n,  var = (sum d^2 - (sum d)^2 / n) / (n - 1),  stddev = sqrt(var),
+//       threshold = mean + stddev_mult * stddev;  outlier iff (double) dist > threshold (a NaN threshold removes nothing).
+//   [PCL-upstream filters/impl/radius_outlier_removal.hpp applyFilterIndices, FLANN RadiusResultSet]  r2 = (float)
+//     (radius * radius), the product in double; a point's neighbours are the OTHER finite points with d2 < r2
+//     (strict, as FLANN's radius set); inlier iff their number >= min_neighbors (PCL: "k <= min_pts is an outlier" with
+//     the point itself in k).
+//   Both: d2 is g_d2's float form, (dx * dx + dy * dy) + dz * dz with nothing fused; lists are ordered by
+//     (d2, index); kept indices ascend; `negative` returns the outliers.
+//   Deviation from PCL: a non-finite point is nobody's neighbour, enters no statistic, gets WM_OUTLIER_NONE and is
+//     returned with neither setting of `negative` (PCL keeps it, with distance 0) -- as wm_set_source drops such points.
+//
+// Launches of a call: pack + bounding box, the grid (count, scan, scatter), then
+//   statistical  k_outlier_mean_dist<K> (knn_search<K> straight into the mean distance: the lists never reach memory),
+//                k_outlier_moments + k_outlier_threshold (the two sums in double, a fixed tree over the points in CALLER
+//                order: the cell sort's order inside a cell is the atomics' arrival order and must not reach a sum)
+//   radius       k_outlier_radius<EXACT> (one lane per query over the rows of the box [q - r, q + r])
+//   both         k_outlier_label, exclusive_scan, k_outlier_compact (kept indices in ascending input order).
+#include "wm_gicp_dev.hpp"
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+
+namespace wm {
+
+namespace {
+
+constexpr int kOutBlock = 64;        // queries (threads) of a search workgroup: one wave, as k_gicp_cov (see there)
+constexpr int kMomBlocksMax = 1024;  // partial rows of the moment sums (their number depends on n alone)
+
+// ------------------------------------------------------------------ statistical: mean distance to the mean_k nearest
+// Queries in the grid's own (cell-sorted) order -- a wave's 64 queries scan the same few rows of cells -- the result
+// stored under the point's caller index (.w).  Only finite points are in the grid; k = mean_k + 1 <= their number.
+template <int K>
+__global__ void __launch_bounds__(kOutBlock) __attribute__((amdgpu_waves_per_eu(K <= 10 ? 6 : (K <= 12 ? 5 : 1))))
+    k_outlier_mean_dist(GridDev g, unsigned n, int k, float r0_cells, float *__restrict__ dist_out) {
+    __shared__ uint2 s_runs[kKnnRows * kOutBlock];
+    const unsigned i = blockIdx.x * kOutBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = g.pts[i];
+    unsigned long long best[K];
+    knn_search<K>(g, q.x, q.y, q.z, k, r0_cells, best, s_runs, threadIdx.x, kOutBlock);
+    double s = 0.0;
+#pragma unroll
+    for (int j = 1; j < K; ++j)
+        if (j < k) s += sqrt((double) __uint_as_float((unsigned) (best[j] >> 32)));
+    dist_out[__float_as_uint(q.w)] = (float) (s / (double) (k - 1));
+}
+
+// sum d and sum d^2 over the finite points, caller order: thread t of the launch takes points t, t + T, ...; a wave's
+// 64 sums by a shuffle tree, a workgroup's four by thread 0 in wave order -> row blockIdx.x of `part`
+__global__ void __launch_bounds__(kBlock)
+    k_outlier_moments(const float4 *__restrict__ pts, const float *__restrict__ dist, unsigned n, double *__restrict__ part) {
+    double s1 = 0.0, s2 = 0.0;
+    const unsigned stride = gridDim.x * kBlock;
+    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const float x = pts[i].x;
+        if (x == x) {
+            const double d = (double) dist[i];
+            s1 += d;
+            s2 += d * d;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_down(s1, off);
+        s2 += __shfl_down(s2, off);
+    }
+    __shared__ double l1[kBlock / 64], l2[kBlock / 64];
+    if ((threadIdx.x & 63) == 0) {
+        l1[threadIdx.x >> 6] = s1;
+        l2[threadIdx.x >> 6] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) {
+            s1 += l1[w];
+            s2 += l2[w];
+        }
+        part[2 * blockIdx.x] = s1;
+        part[2 * blockIdx.x + 1] = s2;
+    }
+}
+
+// the rows added in one fixed order (one wave: lane l takes rows l, l + 64, ..., then the shuffle tree) ->
+// res[0] mean, [1] stddev, [2] threshold
+__global__ void __launch_bounds__(64)
+    k_outlier_threshold(const double *__restrict__ part, unsigned rows, double n_finite, double stddev_mult,
+                        double *__restrict__ res) {
+    double s1 = 0.0, s2 = 0.0;
+    for (unsigned r = threadIdx.x; r < rows; r += 64) {
+        s1 += part[2 * r];
+        s2 += part[2 * r + 1];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_down(s1, off);
+        s2 += __shfl_down(s2, off);
+    }
+    if (threadIdx.x == 0) {
+        const double mean = s1 / n_finite;
+        const double var = (s2 - s1 * s1 / n_finite) / (n_finite - 1.0);
+        const double sd = sqrt(var);
+        res[0] = mean;
+        res[1] = sd;
+        res[2] = mean + stddev_mult * sd;
+    }
+}
+
+// ------------------------------------------------------------------ radius: neighbours within r
+// One lane per query (grid order, result under .w).  The box of cells covering [q - r, q + r] is resolved a batch of
+// kKnnRows rows at a time, as knn_search resolves its rows: a row of x-adjacent cells is ONE contiguous run of the
+// cell-sorted points, the batch's cell_start look-ups are issued together, the non-empty runs go to the lane's column
+// of `runs` (LDS) and are walked in one flat loop with the next candidate's load in flight.  hits counts d2 < r2, the
+// query itself among them (d2 = 0) whenever r2 > 0; the count written is the OTHER points'.
+// EXACT: the count is exact.  Otherwise a lane stops once it has seen `stop` hits (min_neighbors + 1, itself
+// included): what it writes then is >= min_neighbors, which is all the labelling asks.
+template <bool EXACT>
+__global__ void __launch_bounds__(kOutBlock)
+    k_outlier_radius(GridDev g, unsigned n, float r2, float r_cells, unsigned stop, int *__restrict__ count_out) {
+    __shared__ uint2 s_runs[kKnnRows * kOutBlock];
+    const unsigned i = blockIdx.x * kOutBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = g.pts[i];
+    uint2 *runs = s_runs;
+    const unsigned lane_col = threadIdx.x;
+    const float fx = (q.x - g.ox) * g.inv_h, fy = (q.y - g.oy) * g.inv_h, fz = (q.z - g.oz) * g.inv_h;
+    const float rc = r_cells + g.slack;
+    // (clamped as floats: r may exceed what an int holds)
+    const int xa = (int) fmaxf(floorf(fx - rc), 0.f), xb = (int) fminf(floorf(fx + rc), (float) (g.nx - 1));
+    const int ya = (int) fmaxf(floorf(fy - rc), 0.f), yb = (int) fminf(floorf(fy + rc), (float) (g.ny - 1));
+    const int za = (int) fmaxf(floorf(fz - rc), 0.f), zb = (int) fminf(floorf(fz + rc), (float) (g.nz - 1));
+    unsigned hits = 0;
+    const bool any = xa <= xb && ya <= yb && za <= zb;
+    int yy = ya, zz = any ? za : zb + 1;  // row cursor; zz > zb = past the last row
+    while (zz <= zb && (EXACT || hits < stop)) {
+        int n_runs = 0;
+        unsigned rs[kKnnRows], re[kKnnRows];
+#pragma unroll
+        for (int u = 0; u < kKnnRows; ++u) {
+            const bool live = zz <= zb;
+            const size_t base = ((size_t) (live ? zz : za) * g.ny + (live ? yy : ya)) * g.nx;
+            rs[u] = g.cell_start[base + xa];
+            re[u] = live ? g.cell_start[base + xb + 1] : 0u;  // dead row: e <= s
+            if (++yy > yb) {
+                yy = ya;
+                ++zz;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kKnnRows; ++u)
+            if (re[u] > rs[u]) {
+                runs[n_runs * kOutBlock + lane_col] = make_uint2(rs[u], re[u]);
+                ++n_runs;
+            }
+        if (n_runs == 0) continue;
+        int ri = 0;
+        const uint2 r0 = runs[lane_col];
+        unsigned j = r0.x, e = r0.y;
+        float4 t = g.pts[j];
+        for (;;) {
+            bool more = true;
+            if (++j == e) {
+                more = ++ri < n_runs;
+                if (more) {
+                    const uint2 rn = runs[ri * kOutBlock + lane_col];
+                    j = rn.x;
+                    e = rn.y;
+                }
+            }
+            const float4 tn = g.pts[more ? j : r0.x];  // (a lane at its end reads a line it has had already)
+            hits += g_d2(q.x, q.y, q.z, t) < r2 ? 1u : 0u;
+            if (!more || (!EXACT && hits >= stop)) break;
+            t = tn;
+        }
+    }
+    const unsigned self = r2 > 0.f ? 1u : 0u;
+    count_out[__float_as_uint(q.w)] = (int) (hits - (hits >= self ? self : 0u));
+}
+
+// ------------------------------------------------------------------ labels and the kept list (caller order)
+// `thr`: the statistical filter's threshold in device memory (res[2]), nullptr for the radius filter
+__global__ void __launch_bounds__(kBlock)
+    k_outlier_label(const float4 *__restrict__ pts, unsigned n, const float *__restrict__ dist, const double *__restrict__ thr,
+                    const int *__restrict__ counts, int min_neighbors, int negative, uint8_t *__restrict__ labels,
+                    unsigned *__restrict__ keep) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float x = pts[i].x;
+    const bool finite = x == x;
+    bool outlier = false;
+    if (finite) outlier = thr ? (double) dist[i] > *thr : counts[i] < min_neighbors;
+    if (labels) labels[i] = finite ? (outlier ? WM_OUTLIER_OUTLIER : WM_OUTLIER_INLIER) : WM_OUTLIER_NONE;
+    keep[i] = finite && outlier == (negative != 0) ? 1u : 0u;
+}
+
+// pos = the exclusive scan of keep (n + 1 entries); res[3] = the number kept
+__global__ void __launch_bounds__(kBlock)
+    k_outlier_compact(const unsigned *__restrict__ keep, const unsigned *__restrict__ pos, unsigned n, int *__restrict__ out,
+                      size_t cap, double *__restrict__ res) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) res[3] = (double) pos[n];
+    if (i >= n) return;
+    if (keep[i] && pos[i] < cap) out[pos[i]] = (int) i;
+}
+
+__global__ void __launch_bounds__(kBlock) k_outlier_fill(int *__restrict__ p, unsigned n, int v) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+}  // namespace
+
+// The context's workspace of this filter: its own buffers, shared with nothing else on the context.
+struct OutlierWs {
+    DevBuf pts, dist, counts, labels, keep, pos, out, part, res;
+    GridLevel grid;
+    double *h_res = nullptr;  // pinned: mean, stddev, threshold, kept
+};
+
+void outlier_release(wm_ctx *ctx) {
+    OutlierWs *w = static_cast<OutlierWs *>(ctx->outlier);
+    if (!w) return;
+    DevBuf *bufs[] = {&w->pts, &w->dist, &w->counts, &w->labels, &w->keep, &w->pos, &w->out, &w->part, &w->res,
+                      &w->grid.pts, &w->grid.cell_start};
+    for (DevBuf *b : bufs) b->release();
+    if (w->h_res) (void) hipHostFree(w->h_res);
+    delete w;
+    ctx->outlier = nullptr;
+}
+
+namespace {
+
+template <int K>
+int launch_mean_dist(wm_ctx *ctx, const GridDev &g, size_t n, int k, float *dist) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_outlier_mean_dist<K>), dim3((unsigned) ((n + kOutBlock - 1) / kOutBlock)),
+                       dim3(kOutBlock), 0, ctx->stream, g, (unsigned) n, k,
+                       ctx->tune_knn_r0 > 0 ? ctx->tune_knn_r0 : (k <= 12 ? 1.0f : 1.5f), dist);
+    WM_HIP(ctx, hipGetLastError());
+    return WM_OK;
+}
+
+// the K ladder of launch_cov_k / launch_debug_knn_k (wm_gicp.hip)
+int launch_mean_dist_k(wm_ctx *ctx, const GridDev &g, size_t n, int k, float *dist) {
+    if (k <= 8) return launch_mean_dist<8>(ctx, g, n, k, dist);
+    if (k <= 10) return launch_mean_dist<10>(ctx, g, n, k, dist);
+    if (k <= 12) return launch_mean_dist<12>(ctx, g, n, k, dist);
+    if (k <= 16) return launch_mean_dist<16>(ctx, g, n, k, dist);
+    if (k <= 20) return launch_mean_dist<20>(ctx, g, n, k, dist);
+    if (k <= 24) return launch_mean_dist<24>(ctx, g, n, k, dist);
+    return launch_mean_dist<32>(ctx, g, n, k, dist);
+}
+
+uint64_t cells_of(const Bbox &bb, float h) {  // (build_grid_level's lattice)
+    uint64_t c = 1;
+    for (int d = 0; d < 3; ++d) c *= (uint64_t) floor(((double) bb.hi[d] - bb.lo[d]) / h) + 1;
+    return c;
+}
+
+// The call's grid.  The automatic cell is source_grid's (wm_gicp.hip): 1.5 x the cube root of the box's volume per
+// point, rebuilt once when the occupied cells hold more than 6 or fewer than 1.5 points on average.  The radius
+// filter's box [q - r, q + r] must span a bounded number of rows, so its cell is never smaller than `floor_h` =
+// radius / outlier_cell_div (2: at most 6 x 6 rows of at most 6 cells; DESIGN.md 4.8 has the measurements).
+int outlier_grid(wm_ctx *ctx, OutlierWs &w, size_t n, size_t n_finite, const Bbox &bb, float floor_h) {
+    double vol = 1;
+    for (int d = 0; d < 3; ++d) vol *= fmax((double) bb.hi[d] - bb.lo[d], 1e-3);
+    float h = fmaxf((float) fmax(cbrt(vol / (double) n_finite) * 1.5, 1e-4), floor_h);
+    const uint64_t cell_cap = ((uint64_t) 1 << 26) + 8 * (uint64_t) n;  // (a lattice far beyond the points pays for nothing)
+    while (cells_of(bb, h) > cell_cap) h *= 1.26f;
+    double occ = 0;
+    const float4 *pts = w.pts.as<float4>();
+    WM_TRY(build_grid_level(ctx, pts, n, bb, h, &w.grid, &occ));
+    if (occ > 6.0 || (occ > 0 && occ < 1.5)) {
+        float h2 = fmaxf((float) (h * sqrt(3.0 / occ)), floor_h);
+        while (cells_of(bb, h2) > cell_cap) h2 *= 1.26f;
+        if (h2 != h) WM_TRY(build_grid_level(ctx, pts, n, bb, h2, &w.grid, nullptr));
+    }
+    return WM_OK;
+}
+
+bool outlier_params_ok(const wm_outlier_params *p) {
+    if (p->method == WM_OUTLIER_STATISTICAL) return p->mean_k >= 1 && p->mean_k <= 31;
+    if (p->method == WM_OUTLIER_RADIUS) return std::isfinite(p->radius) && p->radius > 0 && p->min_neighbors >= 0;
+    return false;
+}
+
+}  // namespace
+
+}  // namespace wm
+
+using namespace wm;
+
+extern "C" {
+
+void wm_outlier_default_params(wm_outlier_params *p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->method = WM_OUTLIER_STATISTICAL;
+    p->mean_k = 1;         // statistical_outlier_removal.h: mean_k_ (1), std_mul_ (0.0)
+    p->stddev_mult = 0.0;
+    p->radius = 0.0;       // radius_outlier_removal.h: search_radius_ (0.0), min_pts_radius_ (1)
+    p->min_neighbors = 1;
+    p->negative = 0;
+}
+
+int wm_outlier_filter(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const wm_outlier_params *p,
+                      int32_t *indices_out, size_t cap, int out_mem, size_t *n_out, uint8_t *labels_out,
+                      float *mean_dist_out, int32_t *counts_out, wm_outlier_stats *stats) {
+    if (!ctx || !p || !n_out || (n > 0 && !pts) || stride < 12 || (stride & 3) || n > 0x7FFFFFF0u ||
+        (cap > 0 && !indices_out) || (mem != WM_MEM_HOST && mem != WM_MEM_DEVICE) ||
+        (out_mem != WM_MEM_HOST && out_mem != WM_MEM_DEVICE) || !outlier_params_ok(p))
+        return WM_ERR_ARG;
+    *n_out = 0;
+    if (stats) *stats = wm_outlier_stats{};
+    if (n == 0) return WM_OK;
+    const bool stat = p->method == WM_OUTLIER_STATISTICAL;
+    const bool host_out = out_mem == WM_MEM_HOST;
+    WM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->outlier) ctx->outlier = new OutlierWs();
+    OutlierWs &w = *static_cast<OutlierWs *>(ctx->outlier);
+    if (!w.h_res) WM_HIP(ctx, hipHostMalloc((void **) &w.h_res, 4 * sizeof(double), hipHostMallocDefault));
+    hipStream_t st = ctx->stream;
+    const unsigned nblocks = (unsigned) ((n + kBlock - 1) / kBlock);
+
+    // the outputs' places: the caller's own in device memory, else the workspace's
+    WM_HIP(ctx, w.pts.reserve(n * sizeof(float4)));
+    WM_HIP(ctx, w.keep.reserve(n * 4));
+    WM_HIP(ctx, w.pos.reserve((n + 1) * 4));
+    WM_HIP(ctx, w.res.reserve(4 * sizeof(double)));
+    uint8_t *d_labels = nullptr;
+    if (labels_out) {
+        if (host_out) WM_HIP(ctx, w.labels.reserve(n));
+        d_labels = host_out ? w.labels.as<uint8_t>() : labels_out;
+    }
+    float *d_dist = nullptr;
+    int *d_counts = nullptr;
+    if (stat) {
+        if (host_out || !mean_dist_out) WM_HIP(ctx, w.dist.reserve(n * 4));
+        d_dist = (host_out || !mean_dist_out) ? w.dist.as<float>() : mean_dist_out;
+    } else {
+        if (host_out || !counts_out) WM_HIP(ctx, w.counts.reserve(n * 4));
+        d_counts = (host_out || !counts_out) ? w.counts.as<int>() : counts_out;
+    }
+    int *d_out = reinterpret_cast<int *>(indices_out);
+    size_t d_cap = cap;
+    if (host_out) {
+        WM_HIP(ctx, w.out.reserve(n * 4));
+        d_out = w.out.as<int>();
+        d_cap = n;
+    }
+
+    if (stats) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.pts.as<float4>()));
+    Bbox bb;
+    size_t n_finite = 0;
+    WM_TRY(compute_bbox(ctx, w.pts.as<float4>(), n, &bb, &n_finite));
+    if (stats) stats->n_finite = n_finite;
+    // PCL: "Number of points in cloud is less than mean_k": as the k-NN entry points, nothing written
+    if (stat && n_finite > 0 && n_finite < (size_t) p->mean_k + 1) {
+        WM_HIP(ctx, hipStreamSynchronize(st));
+        return WM_NOT_CONVERGED;
+    }
+    // what a non-finite point keeps: label NONE (k_outlier_label writes every label), distance 0, count -1
+    if (stat && mean_dist_out) WM_HIP(ctx, hipMemsetAsync(d_dist, 0, n * 4, st));
+    if (!stat && counts_out) {
+        hipLaunchKernelGGL(k_outlier_fill, dim3(nblocks), dim3(kBlock), 0, st, d_counts, (unsigned) n, -1);
+        WM_HIP(ctx, hipGetLastError());
+    }
+    if (n_finite == 0) {  // nothing to search: the outputs' defaults are the answer
+        if (labels_out) WM_HIP(ctx, hipMemsetAsync(d_labels, 0, n, st));
+        WM_HIP(ctx, hipStreamSynchronize(st));
+        if (host_out) {
+            if (labels_out) WM_HIP(ctx, hipMemcpy(labels_out, d_labels, n, hipMemcpyDeviceToHost));
+            if (stat && mean_dist_out) WM_HIP(ctx, hipMemcpy(mean_dist_out, d_dist, n * 4, hipMemcpyDeviceToHost));
+            if (!stat && counts_out) WM_HIP(ctx, hipMemcpy(counts_out, d_counts, n * 4, hipMemcpyDeviceToHost));
+        }
+        return WM_OK;
+    }
+
+    float r2 = 0.f, rf = 0.f;
+    if (!stat) {
+        r2 = (float) (p->radius * p->radius);
+        rf = sqrtf(r2) * 1.0001f;  // (a point with float d2 < r2 lies within this of the query)
+    }
+    const float div = ctx->tune_outlier_cell_div;
+    WM_TRY(outlier_grid(ctx, w, n, n_finite, bb, stat ? 0.f : fminf((float) p->radius, 1.0e30f) / div));
+    const GridDev &g = w.grid.d;
+
+    WM_HIP(ctx, hipMemsetAsync(w.res.p, 0, 4 * sizeof(double), st));
+    if (stat) {
+        WM_TRY(launch_mean_dist_k(ctx, g, n_finite, p->mean_k + 1, d_dist));
+        const unsigned rows = std::min<unsigned>(nblocks, (unsigned) kMomBlocksMax);
+        WM_HIP(ctx, w.part.reserve((size_t) rows * 2 * sizeof(double)));
+        hipLaunchKernelGGL(k_outlier_moments, dim3(rows), dim3(kBlock), 0, st, w.pts.as<float4>(), (const float *) d_dist,
+                           (unsigned) n, w.part.as<double>());
+        hipLaunchKernelGGL(k_outlier_threshold, dim3(1), dim3(64), 0, st, w.part.as<double>(), rows, (double) n_finite,
+                           p->stddev_mult, w.res.as<double>());
+        WM_HIP(ctx, hipGetLastError());
+    } else {
+        const unsigned sblocks = (unsigned) ((n_finite + kOutBlock - 1) / kOutBlock);
+        const float r_cells = rf * g.inv_h;
+        const unsigned stop = (unsigned) p->min_neighbors + 1u;
+        if (counts_out)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_outlier_radius<true>), dim3(sblocks), dim3(kOutBlock), 0, st, g,
+                               (unsigned) n_finite, r2, r_cells, stop, d_counts);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_outlier_radius<false>), dim3(sblocks), dim3(kOutBlock), 0, st, g,
+                               (unsigned) n_finite, r2, r_cells, stop, d_counts);
+        WM_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_outlier_label, dim3(nblocks), dim3(kBlock), 0, st, w.pts.as<float4>(), (unsigned) n,
+                       (const float *) d_dist, stat ? w.res.as<double>() + 2 : (const double *) nullptr,
+                       (const int *) d_counts, p->min_neighbors, p->negative, d_labels, w.keep.as<unsigned>());
+    WM_HIP(ctx, hipGetLastError());
+    WM_TRY(exclusive_scan(ctx, w.keep.as<unsigned>(), n, w.pos.as<unsigned>()));
+    hipLaunchKernelGGL(k_outlier_compact, dim3(nblocks), dim3(kBlock), 0, st, w.keep.as<unsigned>(), w.pos.as<unsigned>(),
+                       (unsigned) n, d_out, d_cap, w.res.as<double>());
+    WM_HIP(ctx, hipGetLastError());
+    if (stats) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    WM_HIP(ctx, hipMemcpyAsync(w.h_res, w.res.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    WM_HIP(ctx, hipStreamSynchronize(st));
+
+    const size_t kept = (size_t) w.h_res[3];
+    *n_out = kept;
+    if (stats) {
+        stats->n_inliers = p->negative ? n_finite - kept : kept;
+        stats->n_outliers = n_finite - stats->n_inliers;
+        stats->mean = w.h_res[0];
+        stats->stddev = w.h_res[1];
+        stats->threshold = w.h_res[2];
+        (void) hipEventElapsedTime(&stats->kernel_ms, ctx->ev_a, ctx->ev_b);
+    }
+    if (host_out) {
+        const size_t m = std::min(kept, cap);
+        if (m) WM_HIP(ctx, hipMemcpy(indices_out, d_out, m * 4, hipMemcpyDeviceToHost));
+        if (labels_out) WM_HIP(ctx, hipMemcpy(labels_out, d_labels, n, hipMemcpyDeviceToHost));
+        if (stat && mean_dist_out) WM_HIP(ctx, hipMemcpy(mean_dist_out, d_dist, n * 4, hipMemcpyDeviceToHost));
+        if (!stat && counts_out) WM_HIP(ctx, hipMemcpy(counts_out, d_counts, n * 4, hipMemcpyDeviceToHost));
+    }
+    return kept > cap ? WM_ERR_ARG : WM_OK;
+}
+
+}  // extern "C"
