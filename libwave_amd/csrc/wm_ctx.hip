@@ -204,7 +204,7 @@ struct Option {
 };
 constexpr double kIntMin = -2147483648.0, kIntMax = 2147483647.0, kFloatMax = 3.0e38;
 const Option kOptions[] = {
-    // the grid search (wm_nn.hip)
+    // the grid search (wm_nn.hip; the certificate kernel that shares its steps: wm_nn_cert.hip)
     {"lane_lf", "WM_TUNE_LANE_LF", nullptr, &wm_ctx::tune_lane_lf, 0, kFloatMax, kOpenLo},
     {"coop_lf", "WM_TUNE_COOP_LF", nullptr, &wm_ctx::tune_coop_lf, 0, kFloatMax, kOpenLo},
     {"r0", "WM_TUNE_R0", nullptr, &wm_ctx::tune_r0, 0, kFloatMax, kOpenLo},

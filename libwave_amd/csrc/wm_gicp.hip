@@ -566,7 +566,7 @@ struct GicpFn {
 // hosts must never keep each other's remaining workgroups from starting.  A 500k pair takes the whole
 // budget (256 workgroups); the matchers of a MultiMatcher pool working on 20k-point pairs (79
 // workgroups each) get three evaluators side by side, the others launch their evaluations meanwhile.
-// (the budget itself: resident_admit / resident_release, wm_nn.hip -- shared with the resident ICP kernel)
+// (the budget itself: resident_admit / resident_release, wm_nn_cert.hip -- shared with the resident ICP kernel)
 static int gicp_blocks(const wm_ctx *ctx) {
     int nb = (int) ((ctx->n_src + kBlock - 1) / kBlock);
     if (nb > ctx->tune_gicp_blocks) nb = ctx->tune_gicp_blocks;

@@ -1,7 +1,7 @@
 // wm_icp_ctl.hpp -- the scalar side of the ICP iteration loop (icp_run_loop, wm_icp.hip): the record every solve
 // publishes for the host that runs ahead of it, and the policy that picks an iteration's search kernel from those
 // records.  No HIP types: the packers are compiled for the device (publish_step, wm_icp_step.hpp; k_late_solver,
-// wm_nn.hip), the readers and the policy for the host, and all of it by g++ away from any device
+// wm_nn_cert.hip), the readers and the policy for the host, and all of it by g++ away from any device
 // (tests/cpp_host/icp_ctl_host.cpp).  This is the ONE place that knows the words' bit layout.
 #pragma once
 #include <math.h>
@@ -59,7 +59,7 @@ WM_HD unsigned done_word_iterations(unsigned long long w) { return (unsigned) (w
 // ---- which search kernel iteration `it` gets: the full search (k_nn_grid) while the clouds still move, the
 // certificate kernel (k_nn_cert) once a step is a small fraction of a grid cell.  Decided from the record of
 // iteration it - lag alone, so the choice does not depend on when the host looks.  Host only.
-// (The resident kernel leaves by a rule of its own -- k_late_solver, wm_nn.hip -- on the unquantised values of the
+// (The resident kernel leaves by a rule of its own -- k_late_solver, wm_nn_cert.hip -- on the unquantised values of the
 // iteration it has just solved: not this function, and not to be merged with it.)
 struct CertPolicy {
     bool can_cert;          // the certificate kernel may be used at all in this loop

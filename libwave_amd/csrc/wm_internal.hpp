@@ -219,7 +219,7 @@ struct IcpDevState {
     float step_disp;   // upper estimate of how far the last step moved the source points (metres)
     float src_radius;  // half diagonal of the source cloud's bounding box (for step_disp)
     float src_centre[3];
-    // the count of changed matches rides in the fraction of the handled-points sum (units of 2^-24, wm_nn.hip:
+    // the count of changed matches rides in the fraction of the handled-points sum (units of 2^-24, wm_nn_scan.hpp:
     // icp_terms); beyond 2^23 queries per context only every (changed_mask + 1)-th query is counted, so
     // that the fraction can never carry into the integer part, and the count is scaled back up here
     unsigned changed_mask;
@@ -566,13 +566,15 @@ int voxel_downsample_dev(wm_ctx *ctx, const float4 *in, size_t n, float leaf, fl
                          size_t *n_out, const VgKnown *known = nullptr);
 int transform_cloud_dev(wm_ctx *ctx, const float4 *in, size_t n, const double T[16], float4 *out);
 
-// ---- wm_nn.hip
+// ---- wm_nn.hip (the full search, brute force), wm_nn_cert.hip (the certificate kernel, launched and resident)
 // stats_mode < 0: search only; WM_ICP_SVD / WM_ICP_GN6: the search kernel also reduces the ICP
 // statistics of the iteration to *rows_out rows of kAcc doubles in ctx->partials
 int launch_nn_grid(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2,
                    int stats_mode = -1, unsigned *rows_out = nullptr, bool use_bins = false);
 int launch_nn_brute(wm_ctx *ctx, float thr_d2, hipEvent_t ev0, hipEvent_t ev1);
-// the resident form of the certificate kernel (wm_nn.hip: k_nn_cert<.., LATE>): the late iterations in one launch
+// where a search kernel's sums go: the iteration's bins (*bins) or `blocks` rows of ctx->partials (*rows_out)
+int nn_sums_target(wm_ctx *ctx, int stats_mode, bool use_bins, unsigned blocks, long long **bins, unsigned *rows_out);
+// the resident form of the certificate kernel (wm_nn_cert.hip: k_nn_cert<.., LATE>): the late iterations in one launch
 bool late_possible(wm_ctx *ctx, int stats_mode, unsigned *blocks_out);
 size_t late_ctl_bytes();  // sizeof(LateCtl): the developer stamps sit behind it
 int launch_nn_late(wm_ctx *ctx, float thr_d2, int stats_mode, unsigned blocks, bool bounds_valid, unsigned exit_seq,

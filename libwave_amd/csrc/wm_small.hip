@@ -146,7 +146,7 @@ __device__ __forceinline__ unsigned long long sm_key(float d2, unsigned idx) {
     return ((unsigned long long) __float_as_uint(d2) << 32) | idx;
 }
 __device__ __forceinline__ float sm_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
-    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;  // (as canon_d2, wm_nn.hip)
+    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;  // (as canon_d2, wm_nn_scan.hpp)
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 // PCL's float transform of a source point: ((m00*x + m01*y) + m02*z) + m03

@@ -1,4 +1,4 @@
-"""The certificate kernel (k_nn_cert, csrc/wm_nn.hip): late ICP iterations prove per query that the
+"""The certificate kernel (k_nn_cert, csrc/wm_nn_cert.hip): late ICP iterations prove per query that the
 previous match is still the nearest neighbour and search only where the proof fails.  It must give
 the SAME correspondences as a search of every query -- checked against the kd-tree oracle bit for
 bit -- and the same registration as the all-search path.  Replaces

@@ -6,7 +6,9 @@ The shapes are chosen to hit the search's special paths: degenerate extents (pla
 or two grid axes collapse), duplicates (ties resolve to the lowest index), cloud sizes that are
 not multiples of the 4-wide scan group (the reads past a run's end), far-away and huge
 coordinates (box clamping, float cell assignment slack), tiny clouds, dense clumps (long runs)
-and queries with nothing within max_corr (full-radius scans on the coarsest level)."""
+and queries with nothing within max_corr (full-radius scans on the coarsest level).  A few cases run
+a second time with the option nn_balanced = 0: every lane then walks its own candidates (the lane
+scan the library keeps for targets of 2^26 points and more) instead of the wave pooling them."""
 import numpy as np
 import pytest
 
@@ -46,17 +48,30 @@ def _poses():
             np.eye(4)]                                                # warm, no motion at all
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 5, 7, 63, 64, 65, 257, 1001, 4099])
-def test_sizes_not_multiples_of_the_scan_group(wm, ctx, oracle, n):
+def _lane_scan(*values):
+    """The same case again with nn_balanced = 0 (its id says so; the first run keeps its id)."""
+    return pytest.param(*values, 0, id="-".join(str(v) for v in values) + "-lane_scan")
+
+
+@pytest.mark.parametrize("n,balanced", [pytest.param(n, 1, id=str(n)) for n in [1, 2, 3, 5, 7, 63, 64, 65, 257, 1001, 4099]]
+                         + [_lane_scan(65), _lane_scan(4099)])
+def test_sizes_not_multiples_of_the_scan_group(wm, ctx, oracle, n, balanced):
+    if not balanced:
+        ctx.set_option("nn_balanced", 0)
     rng = np.random.default_rng(n)
     tgt = rng.uniform(-2, 2, (n, 3)).astype(np.float32)
     ref = rng.uniform(-2.5, 2.5, (max(n, 50), 3)).astype(np.float32)
     _run(wm, ctx, oracle, ref, tgt, _poses(), 1.0)
 
 
-@pytest.mark.parametrize("shape", ["plane", "line", "point", "two_clumps", "shell"])
-@pytest.mark.parametrize("max_corr", [0.25, 5.0])
-def test_degenerate_and_clumped_targets(wm, ctx, oracle, shape, max_corr):
+@pytest.mark.parametrize("max_corr,shape,balanced",
+                         [pytest.param(m, s, 1, id="%s-%s" % (m, s)) for s in ["plane", "line", "point", "two_clumps", "shell"]
+                          for m in [0.25, 5.0]]
+                         # heavy radii: the cooperative phase runs behind the lane scan too
+                         + [_lane_scan(5.0, "two_clumps"), _lane_scan(5.0, "plane")])
+def test_degenerate_and_clumped_targets(wm, ctx, oracle, shape, max_corr, balanced):
+    if not balanced:
+        ctx.set_option("nn_balanced", 0)
     rng = np.random.default_rng(7)
     n = 30000
     if shape == "plane":
