@@ -89,6 +89,20 @@ class ICPMatcher : public Matcher<PCLPointCloudPtr> {
     ErrorMetric getErrorMetric() const;
     void setNormalK(int k);
 
+    // Correspondence rejection between an iteration's search and its step -- pcl::IterativeClosestPoint::
+    // addCorrespondenceRejector with ONE rejector (no reference counterpart: libwave's ICPMatcher adds none).
+    // Trimmed: pcl::registration::CorrespondenceRejectorTrimmed, `value` = the overlap ratio in [0, 1] (PCL's default
+    // 0.5), at least `min_corr` pairs kept; pairs tied at the cut are all kept.  MedianDistance:
+    // CorrespondenceRejectorMedianDistance, `value` = the factor on the median squared distance (PCL's default 1.0).
+    // For scans that overlap only in part: with max_corr = 3 m the points without a counterpart still find a
+    // "nearest" point and drag the pose.  Either error metric; estimateInfo()'s LUM / Censi then work on the kept
+    // pairs.  A matcher that was never told takes env WAVE_ICP_REJECTOR=trimmed:0.5 or median:1.0, else None.  Not
+    // available with setDevices() of several devices (match() returns false); MultiMatcher queues register such pairs
+    // one after the other inside the batch call.  An invalid value makes match() return false.
+    enum class Rejector { None, Trimmed, MedianDistance };
+    void setRejector(Rejector r, double value, int min_corr = 0);
+    Rejector getRejector() const;
+
     // Spread ONE registration over several GPUs of the node (no reference counterpart): the target is
     // cut into equal-count x-slabs, one per device, every device searches the source points that fall
     // into its slab, and the per-iteration statistics are summed by an RCCL all-reduce over xGMI inside
@@ -138,6 +152,9 @@ class ICPMatcher : public Matcher<PCLPointCloudPtr> {
     PCLPointCloudPtr ref, target;
     int errorMetric = -1;  // WM_ICP_SVD / WM_ICP_PLANE; -1: not told (the environment decides)
     int normalK = 0;
+    int rejector = -1;  // WM_REJECT_*; -1: not told (the environment decides)
+    double rejectValue = 0.0;
+    int rejectMinCorr = 0;
 
     bool ensureContext();
     void estimateLUM();

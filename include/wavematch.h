@@ -102,6 +102,24 @@ enum { /* pcl::registration::DefaultConvergenceCriteria::ConvergenceState */
        /* WM_ICP_PLANE only (no PCL counterpart): J^T J of an iteration is singular to rounding -- the matched normals
         * leave a motion free (one plane: three).  The align ends NOT converged, T_out untouched: loud, not wrong */
        WM_CONV_DEGENERATE = 7 };
+/* Correspondence rejection between an iteration's search and its step (pcl::IterativeClosestPoint::
+ * addCorrespondenceRejector with ONE rejector) [PCL-upstream: restated from PCL 1.8's registration/impl/icp.hpp,
+ * correspondence_rejection_trimmed.cpp and correspondence_rejection_median_distance.cpp; no PCL on the build machine].
+ * Per iteration: C = the matched queries (finite source points with a neighbour inside max_corr), n = |C|, d2_i = the
+ * search's own float squared distance (PCL's Correspondence::distance in ICP).
+ *   WM_REJECT_TRIMMED (CorrespondenceRejectorTrimmed; PCL's defaults: ratio 0.5, min 0)
+ *       k = max((unsigned) floor(reject_ratio * (double) n), reject_min_corr); k >= n: nothing is rejected; k == 0:
+ *       everything is; else t = the k-th smallest d2 (1-based) and a pair is kept iff d2_i <= t.
+ *       DEVIATION from PCL: PCL keeps exactly k pairs (nth_element), which of several pairs tied at the k-th place
+ *       survive being unspecified; here ALL pairs tied at t are kept -- order-independent, kept count >= k.
+ *   WM_REJECT_MEDIAN (CorrespondenceRejectorMedianDistance; PCL's default factor: 1.0)
+ *       m = the element of 0-based rank n / 2 of the ascending d2; kept iff (double) d2_i <= (double) m * reject_factor.
+ * The step, n_corr and the stopping rules' MSE are those of the kept pairs (PCL's rejectors rewrite correspondences_
+ * before min_number_correspondences_, the estimation and the criteria see it); fewer than 3 kept pairs end the align
+ * with WM_CONV_NO_CORRESPONDENCES.  After the align the context's correspondences are the kept pairs of the last
+ * executed iteration (wm_get_correspondences: -1 for a rejected pair, its d2 stays; wm_icp_info's LUM / Censi work on
+ * them).  The threshold is an exact order statistic found on the device (wm_reject.hip): bit-reproducible. */
+enum { WM_REJECT_NONE = 0, WM_REJECT_TRIMMED = 1, WM_REJECT_MEDIAN = 2 };
 
 typedef struct {
     double max_corr;      /* ICPMatcherParams::max_corr, icp.hpp:35 -> icp.cpp:47 */
@@ -123,6 +141,15 @@ typedef struct {
     int profile;          /* HIP-event timing on the ctx stream: 1 = the level-0
                              correspondence kernel only; 2 = every kernel class */
     int normal_k;         /* WM_ICP_PLANE: neighbours per normal, 3 ... 32; 0 = the default, 20 */
+    int reject;           /* WM_REJECT_NONE (default) | WM_REJECT_TRIMMED | WM_REJECT_MEDIAN, every step mode.  A
+                             rejecting align searches in full every iteration (no certificate kernel, no fused sums):
+                             search, select (three histogram passes), filtered sums, solve.  wm_icp_align,
+                             wm_icp_match (every align of every scale) and wm_icp_batch_match (every item through
+                             wm_icp_match inside the call: correct, not fast) take it; the sharded entry points
+                             (wm_icp_shard_*, wm_icp_*_sharded, wm_multi_*) return WM_ERR_ARG */
+    double reject_ratio;  /* WM_REJECT_TRIMMED: the overlap ratio, finite in [0, 1]; default 0.5 */
+    double reject_factor; /* WM_REJECT_MEDIAN: the factor on the median, finite and >= 0; default 1.0 */
+    int reject_min_corr;  /* WM_REJECT_TRIMMED: keep at least this many pairs, >= 0; default 0 */
 } wm_icp_params;
 
 typedef struct {
@@ -165,6 +192,10 @@ typedef struct {
     float late_ms;       /* their duration by HIP events (profile >= 1): search + sums + solve of those iterations */
     int exchange_in_kernel; /* sharded: 1 if the iterations' blocks were exchanged through the ranks' mailboxes inside
                                the solve kernel (one launch per iteration's tail), 0 if by ncclAllReduce between two */
+    int n_matched;       /* the last iteration's matched queries BEFORE rejection (== n_corr without rejection; n_corr
+                            and mse stay what the step used: the kept pairs) */
+    float reject_d2;     /* the last iteration's rejection threshold (kept iff d2 <= it); FLT_MAX: the rule kept
+                            everything, -1: it rejected everything; 0 without rejection */
 } wm_icp_stats;
 
 void wm_icp_default_params(wm_icp_params *p);
@@ -360,6 +391,19 @@ int wm_estimate_normals(wm_ctx *ctx, int which, int k, void *normals_out, int ou
  * correspondences of the last wm_nn_search / align iteration. */
 #define WM_STATS_LEN 32
 int wm_icp_stats_for(wm_ctx *ctx, const double T[16], int mode, double stats[WM_STATS_LEN]);
+
+/* Developer / tests: the element of 0-based rank `rank` of n HOST floats (bit patterns of non-negative floats), found by
+ * the rejection's select kernels (wm_reject.hip).  WM_ERR_ARG unless rank < n < 2^31. */
+int wm_debug_rank_select(wm_ctx *ctx, const float *vals, size_t n, size_t rank, float *out);
+
+/* One iteration's rejection on the correspondences of the last search (wm_nn_search / an align), under pose T:
+ * the threshold, the counts, the kept mask in the caller's order (n_source_input bytes; may be NULL) and the mode's sums
+ * over the kept pairs (may be NULL; layout of wm_icp_stats_for).  reject = WM_REJECT_NONE keeps every matched pair.
+ * all_kept: the rule kept everything whatever the distances (threshold_d2 = FLT_MAX); a rule that rejected everything
+ * reports threshold_d2 = -1.  Leaves the context's correspondences as they are. */
+typedef struct { int n_matched, n_kept; float threshold_d2; int all_kept; } wm_icp_reject_result;
+int wm_icp_reject(wm_ctx *ctx, const double T[16], int mode, int reject, double ratio, double factor, int min_corr,
+                  wm_icp_reject_result *res, unsigned char *kept_out, double stats_out[WM_STATS_LEN]);
 
 /* Host-only solvers on those statistics (no GPU touched; used by every rank
  * after the all-reduce).  Tk_out is the incremental transform of one step:

@@ -23,6 +23,7 @@ WM_GROUND_BATCH_MAX_KEYS = 0xFFFFFFFF  # n_scans * (num_bins_a * num_bins_l + 1)
 WM_GROUND_BATCH_MAX_POINTS = 0x7FFFFFF0  # its scans' points in all
 WM_MEM_HOST, WM_MEM_DEVICE = 0, 1
 WM_ICP_SVD, WM_ICP_GN6, WM_ICP_PLANE = 0, 1, 2
+WM_REJECT_NONE, WM_REJECT_TRIMMED, WM_REJECT_MEDIAN = 0, 1, 2
 WM_NN_AUTO, WM_NN_GRID, WM_NN_BRUTE = 0, 1, 2
 WM_NN_WARM = 0x100
 WM_INFO_LUM, WM_INFO_CENSI, WM_INFO_LUMOLD = 0, 1, 2
@@ -40,7 +41,8 @@ class IcpParams(C.Structure):
     _fields_ = [("max_corr", C.c_double), ("max_iter", C.c_int), ("t_eps", C.c_double),
                 ("fit_eps", C.c_double), ("force_iterations", C.c_int), ("mode", C.c_int),
                 ("nn_method", C.c_int), ("carry_state", C.c_int), ("profile", C.c_int),
-                ("normal_k", C.c_int)]
+                ("normal_k", C.c_int), ("reject", C.c_int), ("reject_ratio", C.c_double),
+                ("reject_factor", C.c_double), ("reject_min_corr", C.c_int)]
 
 
 class IcpStats(C.Structure):
@@ -55,7 +57,11 @@ class IcpStats(C.Structure):
                 ("allreduce_ms", C.c_float), ("n_tgt_local", C.c_uint), ("n_src_local", C.c_uint),
                 ("rccl_ranks", C.c_int), ("shard_attempts", C.c_int),
                 ("late_iterations", C.c_int), ("late_launches", C.c_int), ("late_ms", C.c_float),
-                ("exchange_in_kernel", C.c_int)]
+                ("exchange_in_kernel", C.c_int), ("n_matched", C.c_int), ("reject_d2", C.c_float)]
+
+
+class IcpRejectResult(C.Structure):
+    _fields_ = [("n_matched", C.c_int), ("n_kept", C.c_int), ("threshold_d2", C.c_float), ("all_kept", C.c_int)]
 
 
 class BatchItem(C.Structure):
@@ -254,6 +260,9 @@ def lib():
         L.wm_get_correspondences.argtypes = [C.c_void_p, _ip, _fp, C.c_size_t]
         L.wm_nn_search.argtypes = [C.c_void_p, _dp, C.c_double, C.c_int, _ip, _fp, C.c_size_t, _fp]
         L.wm_icp_stats_for.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
+        L.wm_debug_rank_select.argtypes = [C.c_void_p, _fp, C.c_size_t, C.c_size_t, _fp]
+        L.wm_icp_reject.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                    C.POINTER(IcpRejectResult), C.c_void_p, _dp]
         L.wm_estimate_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.wm_umeyama_from_stats.argtypes = [_dp, _dp]
         L.wm_gn6_from_stats.argtypes = [_dp, _dp]
@@ -458,7 +467,7 @@ class Context:
                     deferred=s.deferred, grid_cell=s.grid_cell,
                     owned_violations=s.owned_violations, cert_launches=s.cert_launches,
                     nn_cert_ms=s.nn_cert_ms, late_iterations=s.late_iterations, late_launches=s.late_launches,
-                    late_ms=s.late_ms)
+                    late_ms=s.late_ms, n_matched=s.n_matched, reject_d2=s.reject_d2)
 
     def icp_match(self, ref, target, res=-1.0, multiscale_steps=0, params=None, **kw):
         """ICPMatcher::match() (icp.cpp:75-133) in one C-ABI call."""
@@ -966,6 +975,28 @@ class Context:
         self._check(lib().wm_icp_stats_for(self._h, T.ctypes.data_as(_dp), int(mode),
                                            st.ctypes.data_as(_dp)), "wm_icp_stats_for")
         return st
+
+    def icp_reject(self, T, mode=WM_ICP_SVD, reject=WM_REJECT_TRIMMED, ratio=0.5, factor=1.0, min_corr=0, want_stats=True):
+        """wm_icp_reject: one iteration's rejection on the correspondences of the last search, under pose T -> dict of
+        n_matched, n_kept, threshold_d2 (float32), all_kept, kept (bool per source point, caller order), stats."""
+        T = np.ascontiguousarray(T, np.float64)
+        r = IcpRejectResult()
+        kept = np.zeros(max(self.n_src, 1), np.uint8)
+        st = np.zeros(WM_STATS_LEN, np.float64)
+        self._check(lib().wm_icp_reject(self._h, T.ctypes.data_as(_dp), int(mode), int(reject), float(ratio), float(factor),
+                                        int(min_corr), C.byref(r), kept.ctypes.data_as(C.c_void_p),
+                                        st.ctypes.data_as(_dp) if want_stats else None), "wm_icp_reject")
+        return dict(n_matched=r.n_matched, n_kept=r.n_kept, threshold_d2=np.float32(r.threshold_d2), all_kept=bool(r.all_kept),
+                    kept=kept[:self.n_src].astype(bool), stats=st if want_stats else None)
+
+    def debug_rank_select(self, vals, rank):
+        """wm_debug_rank_select: the element of 0-based rank `rank` of the float32 array `vals` (non-negative floats),
+        by the rejection's select kernels."""
+        vals = np.ascontiguousarray(vals, np.float32)
+        out = C.c_float(0)
+        self._check(lib().wm_debug_rank_select(self._h, vals.ctypes.data_as(_fp), vals.shape[0], int(rank), C.byref(out)),
+                    "wm_debug_rank_select")
+        return np.float32(out.value)
 
 
 class HostIcp:

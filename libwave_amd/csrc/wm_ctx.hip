@@ -315,7 +315,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
                       &ctx->partials, &ctx->partials2, &ctx->bins, &ctx->nn_bound, &ctx->late_ctl, &ctx->cert_count, &ctx->cert_prof, &ctx->cost_log, &ctx->phase_log, &ctx->shard_ref, &ctx->shard_tgt,
                       &ctx->shard_ref_band, &ctx->shard_tgt_band, &ctx->shard_misc, &ctx->shard_flags, &ctx->shard_pos_t,
                       &ctx->shard_pos_s, &ctx->shard_stats, &ctx->ndt_sum_dev, &ctx->corr_tmp_idx, &ctx->corr_tmp_d2, &ctx->d_state,
-                      &ctx->plane_nrm, &ctx->plane_nrm_src, &ctx->plane_bins};
+                      &ctx->plane_nrm, &ctx->plane_nrm_src, &ctx->plane_bins, &ctx->reject_buf, &ctx->reject_tmp};
     for (DevBuf *b : bufs) b->release();
     ctx->icp_stage.release();
     ctx->gicp_stage.release();

@@ -51,8 +51,11 @@ template <int MODE>
 __global__ void __launch_bounds__(kBlock)
     k_icp_stats(const float4 *__restrict__ src, unsigned n,
                 const unsigned long long *__restrict__ keys, const float4 *__restrict__ tgt,
-                const IcpDevState *__restrict__ st, double *__restrict__ partials) {
+                const IcpDevState *__restrict__ st, double *__restrict__ partials, const int *__restrict__ rej) {
     if (st->done) return;
+    // correspondence rejection (wm_reject.hip): a matched pair counts iff its d2's bit pattern is <= the threshold's
+    // (signed: "reject everything" is a negative one); no rejection: no d2 is above INT_MAX
+    const int rej_thr = rej ? *rej : 0x7FFFFFFF;
     double a[kAcc];
 #pragma unroll
     for (int k = 0; k < kAcc; ++k) a[k] = 0.0;
@@ -83,6 +86,7 @@ __global__ void __launch_bounds__(kBlock)
             const unsigned long long key = keyv[u];
             const unsigned idx = (unsigned) key;
             if (idx == kNoIdx) continue;
+            if ((int) (unsigned) (key >> 32) > rej_thr) continue;  // rejected
             const float4 q4 = q4v[u];
             const double px = fx, py = fy, pz = fz, qx = q4.x, qy = q4.y, qz = q4.z;
             const double d2 = (double) __uint_as_float((unsigned) (key >> 32));
@@ -455,7 +459,9 @@ static int stat_blocks(size_t n) {
     return (int) b;
 }
 
-static int launch_stats(wm_ctx *ctx, int mode) {
+unsigned stat_rows(const wm_ctx *ctx) { return (unsigned) stat_blocks(ctx->n_src); }
+
+int launch_stats(wm_ctx *ctx, int mode, const int *rej) {
     const unsigned n = (unsigned) ctx->n_src;
     const int nb = stat_blocks(n);
     const IcpDevState *st = ctx->d_state.as<IcpDevState>();
@@ -463,12 +469,12 @@ static int launch_stats(wm_ctx *ctx, int mode) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_icp_stats<WM_ICP_SVD>), dim3(nb), dim3(kBlock), 0,
                            ctx->stream, ctx->src_sorted.as<float4>(), n,
                            ctx->keys.as<unsigned long long>(), ctx->match_pt.as<float4>(), st,
-                           ctx->partials.as<double>());
+                           ctx->partials.as<double>(), rej);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_icp_stats<WM_ICP_GN6>), dim3(nb), dim3(kBlock), 0,
                            ctx->stream, ctx->src_sorted.as<float4>(), n,
                            ctx->keys.as<unsigned long long>(), ctx->match_pt.as<float4>(), st,
-                           ctx->partials.as<double>());
+                           ctx->partials.as<double>(), rej);
     WM_HIP(ctx, hipGetLastError());
     return WM_OK;
 }
@@ -516,6 +522,8 @@ static int launch_reduce_solve(wm_ctx *ctx, unsigned rows, double *stats_io, uns
     WM_HIP(ctx, hipGetLastError());
     return WM_OK;
 }
+
+int launch_sum_rows(wm_ctx *ctx) { return launch_reduce_solve<1>(ctx, stat_rows(ctx), nullptr); }
 
 void init_state(IcpDevState *s, const double *T, const wm_icp_params *p, double prev_mse) {
     memset(s, 0, sizeof(*s));
@@ -568,6 +576,8 @@ static void stats_from_state(const IcpDevState &s, wm_icp_stats *stats) {
     stats->mse = s.mse;
     stats->prev_mse = s.prev_mse;
     stats->owned_violations = s.owned_violations;
+    stats->n_matched = s.n_corr;  // (no rejection; a rejecting loop's finish() knows better)
+    stats->reject_d2 = 0.f;
 }
 
 namespace {
@@ -664,6 +674,9 @@ struct IcpLoop {
     // point-to-plane (wm_plane.hip): a search-only launch, the plane sums, their solve.  Always the FULL search: the
     // certificate kernel's policy is steered by counts only the fused statistics carry.
     const bool plane;
+    // correspondence rejection (wm_reject.hip): a search-only launch, the select, the filtered sums, their solve.  Always
+    // the FULL search, no fused sums, no bins for SVD / GN6.
+    const bool reject;
     const bool slab;
     // the grid path adds its sums into bins (wm_bins.hpp) and solves from them -- k_bins_solve, or, sharded, the
     // k_reduce_solve that carries the exchange: no k_reduce_rows, no rows of partial sums
@@ -679,13 +692,14 @@ struct IcpLoop {
 
     static bool can_cert(const wm_ctx *ctx, const wm_icp_params *p, bool brute) {
         return !brute && ctx->tune_nn_balanced && ctx->tune_cert_from >= -1 && ctx->n_tgt_input < (1u << 26) - 8u &&
-               !ctx->cost_log.p && p->mode != WM_ICP_PLANE;
+               !ctx->cost_log.p && p->mode != WM_ICP_PLANE && p->reject == WM_REJECT_NONE;
     }
     IcpLoop(wm_ctx *c, const wm_icp_params *p_, bool brute_, float thr_, wm_comm *comm_, double *blk_)
         : ctx(c), p(p_), brute(brute_), thr(thr_), comm(comm_), blk(blk_),
           max_it(p_->force_iterations > 0 ? p_->force_iterations : p_->max_iter), nb(stat_blocks(c->n_src)),
           kLag(c->tune_lag >= 1 && c->tune_lag <= 16 ? c->tune_lag : 2), plane(p_->mode == WM_ICP_PLANE),
-          slab(c->h_state->slab_on != 0), use_bins(!brute_ && c->tune_bins != 0 && !c->cost_log.p && !plane),
+          reject(p_->reject != WM_REJECT_NONE), slab(c->h_state->slab_on != 0),
+          use_bins(!brute_ && c->tune_bins != 0 && !c->cost_log.p && !plane && !reject),
           cert_thr(brute_ ? 0.f : c->tune_cert_disp * c->levels[0].d.h),
           late_ok(can_cert(c, p_, brute_) && c->tune_late && !blk_ && !slab && !c->cert_count.p && !c->cert_prof.p),
           policy(can_cert(c, p_, brute_), c->tune_cert_from, cert_thr, c->tune_cert_changed, c->tune_cert_unsettled, kLag,
@@ -708,6 +722,7 @@ struct IcpLoop {
         memset(ctx->h_pub, 0, sizeof(unsigned long long) * (size_t) (max_it + 1));
         in_kernel_exchange = blk && comm_exchange_args(comm, &xchg) == WM_OK;
         ctx->cert_launches = 0;
+        if (reject) WM_TRY(reject_ready(ctx));
         if (use_bins) {
             WM_TRY(bins_ready(ctx));  // (zeroes them if the last loop left them dirty)
             ctx->bins_dirty = true;   // (until this loop has ended normally)
@@ -799,6 +814,15 @@ struct IcpLoop {
     // iteration `it`'s correspondences and its sums: *rows rows of partials, the bins, or (plane) the plane bins
     int enqueue_search(int it, bool cert_on, unsigned *rows) {
         *rows = (unsigned) nb;
+        if (reject) {
+            if (blk) return WM_ERR_ARG;  // (not sharded: the entry points refuse it)
+            if (brute) WM_TRY(launch_nn_brute(ctx, thr, ev.e0, ev.e1));
+            else WM_TRY(launch_nn_grid(ctx, thr, ev.e0, ev.e1, ev.e1b, -1, nullptr, false));
+            if (brute) WM_TRY(ev.record(ev.e1b));
+            WM_TRY(launch_reject_select(ctx, ctx->keys.as<unsigned long long>(), (unsigned) ctx->n_src, p->reject, p->reject_ratio,
+                                        p->reject_factor, (unsigned) p->reject_min_corr, 0u));
+            return plane ? launch_plane_stats(ctx, reject_threshold(ctx)) : launch_stats(ctx, p->mode, reject_threshold(ctx));
+        }
         if (plane) {
             if (blk) return WM_ERR_ARG;  // (not sharded: the entry points refuse the mode)
             if (brute) WM_TRY(launch_nn_brute(ctx, thr, ev.e0, ev.e1));
@@ -862,6 +886,8 @@ struct IcpLoop {
             WM_HIP(ctx, hipGetLastError());
         }
         if (ctx->cert_launches > 0) WM_TRY(launch_fix_keys(ctx, thr));
+        // the keys become the kept pairs only now: while the loop ran, an iteration's keys seeded the next search
+        if (reject) WM_TRY(launch_reject_mark(ctx));
         WM_TRY(download_state(ctx));
         WM_HIP(ctx, hipEventRecord(ctx->ev_b, ctx->stream));
         WM_HIP(ctx, hipEventSynchronize(ctx->ev_b));
@@ -889,6 +915,10 @@ struct IcpLoop {
             stats->late_iterations = ctx->late_iters;
             stats->late_launches = ctx->late_launches;
             stats->exchange_in_kernel = in_kernel_exchange ? 1 : 0;
+            if (reject) {
+                stats->n_matched = s.n_matched;
+                memcpy(&stats->reject_d2, &s.reject_bits, sizeof(float));
+            }
             (void) hipEventElapsedTime(&stats->align_ms, ctx->ev_a, ctx->ev_b);
             ev.read_back(s, blk != nullptr, stats);
         }
@@ -1000,6 +1030,10 @@ void wm_icp_default_params(wm_icp_params *p) {
     p->mode = WM_ICP_SVD;
     p->nn_method = WM_NN_AUTO;
     p->carry_state = 1;
+    p->reject = WM_REJECT_NONE;
+    p->reject_ratio = 0.5;   // CorrespondenceRejectorTrimmed's overlap_ratio_
+    p->reject_factor = 1.0;  // CorrespondenceRejectorMedianDistance's factor_
+    p->reject_min_corr = 0;
 }
 
 int wm_icp_align(wm_ctx *ctx, const wm_icp_params *p, double T_out[16], wm_icp_stats *stats) {
@@ -1007,6 +1041,7 @@ int wm_icp_align(wm_ctx *ctx, const wm_icp_params *p, double T_out[16], wm_icp_s
     if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6 && p->mode != WM_ICP_PLANE)) return WM_ERR_ARG;
     if (p->force_iterations <= 0 && p->max_iter <= 0) return WM_ERR_ARG;
     if (p->mode == WM_ICP_PLANE && (plane_normal_k(p->normal_k) < 3 || plane_normal_k(p->normal_k) > 32)) return WM_ERR_ARG;
+    if (!reject_params_ok(p->reject, p->reject_ratio, p->reject_factor, p->reject_min_corr)) return WM_ERR_ARG;
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (ctx->n_src_input == 0 || ctx->n_tgt_input == 0) {
@@ -1071,6 +1106,7 @@ int wm_icp_match(wm_ctx *ctx, const void *ref, size_t n_ref, const void *target,
     if (!ctx || !p || !T_out || (n_ref > 0 && !ref) || (n_target > 0 && !target) || stride < 12 ||
         (stride & 3) || n_ref > 0x7FFFFFF0u || n_target > 0x7FFFFFF0u)
         return WM_ERR_ARG;
+    if (!reject_params_ok(p->reject, p->reject_ratio, p->reject_factor, p->reject_min_corr)) return WM_ERR_ARG;
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (!(res > 0)) {  // icp.cpp:123-131
@@ -1147,6 +1183,7 @@ int wm_icp_shard_begin(wm_ctx *ctx, const wm_icp_params *p, double x_lo, double 
     // sharded registration: it contributes zeros)
     if (!ctx || !p || !(p->max_corr > 0) || !(x_lo <= x_hi)) return WM_ERR_ARG;
     if (p->mode == WM_ICP_PLANE) return WM_ERR_ARG;  // (the plane metric is not sharded)
+    if (p->reject != WM_REJECT_NONE) return WM_ERR_ARG;  // (nor is correspondence rejection)
     if (ctx->n_src_input == 0 && expect_owned_total == 0) return WM_ERR_STATE;
     WM_TRY(shard_begin(ctx, p, x_lo, x_hi, (double) expect_owned_total, 0.0, nullptr, nullptr, DBL_MAX));
     WM_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -225,6 +225,9 @@ struct IcpDevState {
     unsigned changed_mask;
     int uns_global;  // sharded: the count of searched queries came through the all-reduced block (all ranks steer alike)
     int xchg_failed;  // sharded, in-kernel exchange (wm_xchg.hpp): a peer's block never arrived; the registration ended there
+    // correspondence rejection (wm_reject.hip): the last executed iteration's matched count and threshold bits, copied
+    // here by the kernel that ends a rejecting loop (k_reject_mark); 0 otherwise
+    int n_matched, reject_bits;
     int pad_;
 };
 
@@ -391,6 +394,10 @@ struct wm_ctx {
     wm::DevBuf plane_nrm, plane_nrm_src, plane_bins;
     bool plane_nrm_valid = false;
     int plane_nrm_k = 0;
+
+    // correspondence rejection (wm_reject.hip): the select's histograms, tickets and record; scratch of the two
+    // developer entry points (keys built from floats, the kept mask)
+    wm::DevBuf reject_buf, reject_tmp;
 
     // NDT voxel model of the target
     wm::DevBuf ndt_keys, ndt_keys2, ndt_vox, ndt_vkey, ndt_hkeys, ndt_hvals, ndt_dense, ndt_meanf, ndt_vsum;
@@ -631,8 +638,22 @@ constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller sa
 int plane_normal_k(int k);          // 0 -> the default
 int plane_target_normals(wm_ctx *ctx, int k);  // the target's normals on the context (cached per target and k)
 int plane_bins_ready(wm_ctx *ctx);
-int launch_plane_stats(wm_ctx *ctx);  // after a search-only launch: the 29 sums into the plane bins
+int launch_plane_stats(wm_ctx *ctx, const int *rej = nullptr);  // after a search-only launch: the 29 sums into the plane bins
 int launch_plane_solve(wm_ctx *ctx, unsigned long long *pub, int pub_slots, int solve);  // solve == 0: the sums into st->stats only
+
+// ---- wm_reject.hip: correspondence rejection (wm_icp_params.reject)
+bool reject_params_ok(int reject, double ratio, double factor, int min_corr);  // the valid ranges of wavematch.h
+int reject_ready(wm_ctx *ctx);  // the select's histograms and tickets: allocated and all zero
+// the threshold of the keys' matched pairs under the rule (WM_REJECT_*; -1: the element of rank `rank`), left on the
+// device: three histogram passes; returns at once on st->done
+int launch_reject_select(wm_ctx *ctx, const unsigned long long *keys, unsigned n, int rule, double ratio, double factor,
+                         unsigned min_corr, unsigned rank);
+const int *reject_threshold(const wm_ctx *ctx);  // where that threshold's bit pattern is (what the filtered sums read)
+int launch_reject_mark(wm_ctx *ctx);  // behind a loop's last iteration: rejected keys lose their index, the record -> the state
+// the statistics kernels (wm_icp.hip, wm_plane.hip) with the filter: rej = reject_threshold(ctx) or nullptr
+int launch_stats(wm_ctx *ctx, int mode, const int *rej = nullptr);
+unsigned stat_rows(const wm_ctx *ctx);  // rows of partial sums launch_stats leaves
+int launch_sum_rows(wm_ctx *ctx);       // ... added up into st->stats (no solve)
 
 // ---- wm_gicp.hip
 int source_grid(wm_ctx *ctx);  // the source's own search grid (ctx->src_grid), built over src_orig

@@ -147,8 +147,11 @@ static_assert(kGnG + 6 == kPlaneComps && kPlaneComps < (int) kBinPoison, "the GN
 __global__ void __launch_bounds__(kBlock)
     k_plane_stats(const float4 *__restrict__ src, unsigned n, const unsigned long long *__restrict__ keys,
                   const float4 *__restrict__ match_pt, const float4 *__restrict__ normals, unsigned n_normals,
-                  const IcpDevState *__restrict__ st, long long *__restrict__ bins) {
+                  const IcpDevState *__restrict__ st, long long *__restrict__ bins, const int *__restrict__ rej) {
     if (st->done) return;
+    // correspondence rejection (wm_reject.hip): a matched pair counts iff its d2's bit pattern is <= the threshold's
+    // (signed: "reject everything" is a negative one); no rejection: no d2 is above INT_MAX
+    const int rej_thr = rej ? *rej : 0x7FFFFFFF;
     double a[kPlaneComps];
 #pragma unroll
     for (int k = 0; k < kPlaneComps; ++k) a[k] = 0.0;
@@ -178,6 +181,7 @@ __global__ void __launch_bounds__(kBlock)
             const unsigned long long key = keyv[u];
             const unsigned idx = (unsigned) key;
             if (idx >= n_normals) continue;  // kNoIdx: no match within max_corr
+            if ((int) (unsigned) (key >> 32) > rej_thr) continue;  // rejected
             // the source point under the pose the search used: the search kernels' float arithmetic
             const float4 p4 = pv[u];
             const float fx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p4.x), __fmul_rn(T[1], p4.y)), __fmul_rn(T[2], p4.z)), T[3]);
@@ -226,7 +230,7 @@ int plane_bins_ready(wm_ctx *ctx) {  // the plane pass's own bins: zero before a
     return WM_OK;
 }
 
-int launch_plane_stats(wm_ctx *ctx) {
+int launch_plane_stats(wm_ctx *ctx, const int *rej) {
     const unsigned n = (unsigned) ctx->n_src;
     if (n == 0) return WM_OK;
     if (!ctx->plane_bins.p || !ctx->plane_nrm_valid) return WM_ERR_STATE;
@@ -234,7 +238,7 @@ int launch_plane_stats(wm_ctx *ctx) {
     if (blocks > (unsigned) kPlaneMaxBlocks) blocks = kPlaneMaxBlocks;
     hipLaunchKernelGGL(k_plane_stats, dim3(blocks), dim3(kBlock), 0, ctx->stream, ctx->src_sorted.as<float4>(), n,
                        ctx->keys.as<unsigned long long>(), ctx->match_pt.as<float4>(), ctx->plane_nrm.as<float4>(),
-                       (unsigned) ctx->n_tgt_input, ctx->d_state.as<IcpDevState>(), ctx->plane_bins.as<long long>());
+                       (unsigned) ctx->n_tgt_input, ctx->d_state.as<IcpDevState>(), ctx->plane_bins.as<long long>(), rej);
     WM_HIP(ctx, hipGetLastError());
     return WM_OK;
 }

@@ -829,6 +829,7 @@ static int align_sharded_impl(wm_ctx *ctx, wm_comm *comm, const void *ref, size_
         n_ref > 0x7FFFFFF0u || n_target > 0x7FFFFFF0u || !(p->max_corr > 0))
         return WM_ERR_ARG;
     if (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6) return WM_ERR_ARG;
+    if (p->reject != WM_REJECT_NONE) return WM_ERR_ARG;  // (correspondence rejection is not sharded)
     if (p->force_iterations <= 0 && p->max_iter <= 0) return WM_ERR_ARG;
     const int world = comm ? comm->world : 1, rank = comm ? comm->rank : 0;
     if (world == 1 && !(comm && comm->nccl && ctx->tune_force_shard)) {  // nothing to shard
@@ -1025,6 +1026,7 @@ int wm_icp_match_sharded(wm_ctx *ctx, wm_comm *comm, const void *ref, size_t n_r
     if (!ctx || !p || !T_out || (n_ref > 0 && !ref) || (n_target > 0 && !target) || stride < 12 || (stride & 3) ||
         n_ref > 0x7FFFFFF0u || n_target > 0x7FFFFFF0u)
         return WM_ERR_ARG;
+    if (p->reject != WM_REJECT_NONE) return WM_ERR_ARG;
     if (!(res > 0)) return wm_icp_align_sharded(ctx, comm, ref, n_ref, target, n_target, stride, mem, p, T_out, stats);
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1122,6 +1124,7 @@ int wm_multi_icp_match(wm_multi *m, const void *ref, size_t n_ref, const void *t
                        size_t stride, const wm_icp_params *p, float res, int multiscale_steps, double T_out[16],
                        wm_icp_stats *stats) {
     if (!m || !p || !T_out) return WM_ERR_ARG;
+    if (p->reject != WM_REJECT_NONE) return WM_ERR_ARG;  // (a group of one included: the same answer whatever its size)
     const int n = (int) m->ctx.size();
     if (n == 1)
         return wm_icp_match(m->ctx[0], ref, n_ref, target, n_target, stride, WM_MEM_HOST, p, res, multiscale_steps, T_out,

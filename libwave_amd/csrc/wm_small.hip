@@ -965,6 +965,7 @@ void small_fill_stats(const SmallResult &r, float kernel_ms, wm_icp_stats *s) {
     s->iterations = r.iterations;
     s->state = r.state;
     s->n_corr = r.n_corr;
+    s->n_matched = r.n_corr;  // (no rejection on this path)
     s->mse = r.mse;
     s->prev_mse = r.prev_mse;
     s->align_ms = kernel_ms;  // (the whole batch's launch)
@@ -988,9 +989,10 @@ int wm_icp_batch_match(wm_ctx *ctx, const wm_batch_item *items, int n_items, siz
     if (!(p->max_corr > 0) || (p->mode != WM_ICP_SVD && p->mode != WM_ICP_GN6 && p->mode != WM_ICP_PLANE)) return WM_ERR_ARG;
     if (p->force_iterations <= 0 && p->max_iter <= 0) return WM_ERR_ARG;
     if (with_info != 0 && with_info != 1) return WM_ERR_ARG;
+    if (!reject_params_ok(p->reject, p->reject_ratio, p->reject_factor, p->reject_min_corr)) return WM_ERR_ARG;
     if (n_items == 0) return WM_OK;
-    if (p->mode == WM_ICP_PLANE) {
-        // the one-workgroup registrations know no normals: every item is registered by wm_icp_match inside the call, the
+    if (p->mode == WM_ICP_PLANE || p->reject != WM_REJECT_NONE) {
+        // the one-workgroup registrations know no normals and no rejection: every item is registered by wm_icp_match inside the call, the
         // route oversize items take -- correct, not fast
         for (int k = 0; k < n_items; ++k) {
             const wm_batch_item &it = items[k];

@@ -60,6 +60,53 @@ ICPMatcher::ErrorMetric ICPMatcher::getErrorMetric() const {
 
 void ICPMatcher::setNormalK(int k) { normalK = k; }
 
+namespace {
+// the rejector of matchers that were not told (ICPMatcher::setRejector): env WAVE_ICP_REJECTOR=trimmed:<ratio> or
+// median:<factor> (the value may be left out: PCL's defaults, 0.5 and 1.0)
+struct EnvRejector {
+    int kind;
+    double value;
+};
+const EnvRejector &envRejector() {
+    static const EnvRejector v = [] {
+        EnvRejector r{WM_REJECT_NONE, 0.0};
+        const char *e = std::getenv("WAVE_ICP_REJECTOR");
+        if (!e) return r;
+        const std::string s(e);
+        const size_t colon = s.find(':');
+        const std::string name = s.substr(0, colon);
+        if (name == "trimmed") r = EnvRejector{WM_REJECT_TRIMMED, 0.5};
+        else if (name == "median") r = EnvRejector{WM_REJECT_MEDIAN, 1.0};
+        else return r;
+        if (colon != std::string::npos && colon + 1 < s.size()) r.value = std::atof(s.c_str() + colon + 1);
+        return r;
+    }();
+    return v;
+}
+}  // namespace
+
+void ICPMatcher::setRejector(Rejector r, double value, int min_corr) {
+    rejector = r == Rejector::Trimmed ? WM_REJECT_TRIMMED : (r == Rejector::MedianDistance ? WM_REJECT_MEDIAN : WM_REJECT_NONE);
+    rejectValue = value;
+    rejectMinCorr = min_corr;
+}
+
+ICPMatcher::Rejector ICPMatcher::getRejector() const {
+    const int r = rejector >= 0 ? rejector : envRejector().kind;
+    return r == WM_REJECT_TRIMMED ? Rejector::Trimmed : (r == WM_REJECT_MEDIAN ? Rejector::MedianDistance : Rejector::None);
+}
+
+namespace {
+// the matcher's rejector (or the environment's, for one that was never told) -> the parameters of a registration
+void applyRejector(int rejector, double rejectValue, int rejectMinCorr, wm_icp_params &p) {
+    p.reject = rejector >= 0 ? rejector : envRejector().kind;
+    const double value = rejector >= 0 ? rejectValue : envRejector().value;
+    if (p.reject == WM_REJECT_TRIMMED) p.reject_ratio = value;
+    if (p.reject == WM_REJECT_MEDIAN) p.reject_factor = value;
+    p.reject_min_corr = rejector >= 0 ? rejectMinCorr : 0;
+}
+}  // namespace
+
 ICPMatcherParams::ICPMatcherParams(const std::string &config_path) {
     int estimator = 0;
     // `fit_eps` is deliberately absent: the reference's loader never reads it (icp.cpp:9-16)
@@ -89,7 +136,7 @@ ICPMatcher::ICPMatcher(ICPMatcherParams params1)
 ICPMatcher::ICPMatcher(const ICPMatcher &o)
     : Matcher<PCLPointCloudPtr>(o), params(o.params), ctx(nullptr), multi(nullptr), devices(o.devices),
       device(o.device), converged(false), lastMatch(kNone), ref(o.ref), target(o.target), errorMetric(o.errorMetric),
-      normalK(o.normalK) {}
+      normalK(o.normalK), rejector(o.rejector), rejectValue(o.rejectValue), rejectMinCorr(o.rejectMinCorr) {}
 
 ICPMatcher &ICPMatcher::operator=(const ICPMatcher &o) {
     if (this == &o) return *this;
@@ -106,6 +153,9 @@ ICPMatcher &ICPMatcher::operator=(const ICPMatcher &o) {
     target = o.target;
     errorMetric = o.errorMetric;
     normalK = o.normalK;
+    rejector = o.rejector;
+    rejectValue = o.rejectValue;
+    rejectMinCorr = o.rejectMinCorr;
     return *this;
 }
 
@@ -144,6 +194,7 @@ bool ICPMatcher::match() {
     p.carry_state = 1;             // one PCL object per matcher: its criteria remember the last MSE
     p.mode = errorMetric >= 0 ? errorMetric : envErrorMetric();
     p.normal_k = normalK;
+    applyRejector(rejector, rejectValue, rejectMinCorr, p);
     if (const int forced = benchForceIterations()) {  // (bench only: see setBenchForceIterations)
         p.force_iterations = forced;
         p.max_iter = std::max(p.max_iter, forced);
@@ -227,6 +278,7 @@ bool ICPMatcher::matchBatch(const std::vector<std::pair<PCLPointCloudPtr, PCLPoi
     p.fit_eps = params.fit_eps;
     p.mode = errorMetric >= 0 ? errorMetric : envErrorMetric();
     p.normal_k = normalK;
+    applyRejector(rejector, rejectValue, rejectMinCorr, p);
     const size_t n = pairs.size();
     std::vector<wm_batch_item> items(n);
     for (size_t k = 0; k < n; ++k) {
