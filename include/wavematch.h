@@ -800,6 +800,54 @@ int wm_outlier_filter(wm_ctx *ctx, const void *pts, size_t n, size_t stride_byte
                       int32_t *counts_out /* NULL ok, radius; -1 for a non-finite point */,
                       wm_outlier_stats *stats /* NULL ok */);
 
+/* ------------------------------------------------------------- Euclidean cluster extraction */
+/* pcl::EuclideanClusterExtraction on the device: the step between GroundSegmentation's obstacle points and a
+ * registration.  [PCL-upstream: restated from PCL 1.8 segmentation/impl/extract_clusters.hpp; no PCL on the build
+ * machine]  (tests/cluster_reference.py is the checker):
+ *   edges        r2 = (float) (tolerance * tolerance), the product formed in double; two different finite points are
+ *                joined iff d2 < r2 (strict, as FLANN's radius set under PCL's clustering), d2 = (dx * dx + dy * dy) +
+ *                dz * dz in float with every operation rounded and nothing fused.  That form is symmetric in its two
+ *                points: the relation is an undirected graph.
+ *   clusters     PCL's region growing (extractEuclideanClusters) returns that graph's connected components, whatever
+ *                the seed order.  A component is grown in full and kept iff max(min_cluster_size, 1) <= size <=
+ *                max_cluster_size; max < min is legal and keeps nothing.
+ *   order        clusters by size, largest first (EuclideanClusterExtraction::extract sorts them so); inside a cluster
+ *                the indices ascend (PCL sorts them).  Cluster c is indices_out[offsets_out[c] .. offsets_out[c + 1]);
+ *                labels_out[i] is c, WM_CLUSTER_REJECTED or WM_CLUSTER_NONE.
+ *   deviations   PCL leaves the order of equal-sized clusters to std::sort: here equal sizes go by their smallest
+ *                member index, ascending.  A non-finite point is nobody's neighbour and is in no cluster
+ *                (WM_CLUSTER_NONE), exactly as in wm_outlier_filter.
+ *   determinism  every output byte is a function of the input array alone; two calls give identical bytes. */
+typedef struct {
+    double tolerance;      /* setClusterTolerance: metres, finite and > 0 */
+    int min_cluster_size;  /* setMinClusterSize, >= 0 (0 acts as 1); PCL's default 1 */
+    int max_cluster_size;  /* setMaxClusterSize, >= 0; PCL's default INT_MAX */
+} wm_cluster_params;
+void wm_cluster_default_params(wm_cluster_params *p);   /* PCL's: 0, 1, INT_MAX (tolerance must then be set) */
+
+enum { WM_CLUSTER_NONE = -1 /* non-finite point */, WM_CLUSTER_REJECTED = -2 /* its component is outside [min, max] */ };
+typedef struct {
+    size_t n_finite, n_components /* before the size rule */, n_clusters, n_clustered /* points in kept clusters */,
+        largest /* points of the largest KEPT cluster, 0 without one */;
+    float kernel_ms;   /* pack to the last output, as wm_outlier_stats.kernel_ms */
+} wm_cluster_stats;
+
+/* One extraction over n records of `stride_bytes` (x y z first) in `mem`.  *n_clusters and *n_out: the kept clusters
+ * and their points.  More kept points than `cap`, or more clusters than `cap_clusters`: WM_ERR_ARG with *n_out and
+ * *n_clusters the true counts, the first `cap` indices and the first cap_clusters + 1 offsets written, the offsets
+ * clamped to `cap`.  `out_mem` says where the three output arrays live.  Argument errors are found before a device is
+ * touched: a null ctx / p / n_out / n_clusters, a bad stride, mem or out_mem, n > 0x7FFFFFF0, a tolerance that is not
+ * finite or <= 0, negative sizes, a null array with a non-zero capacity.  n == 0 or a cloud without a finite point:
+ * WM_OK with zero clusters and offsets_out[0] = 0 (for n == 0 no device is touched, so offsets_out[0] is written only
+ * where out_mem is WM_MEM_HOST).  The grid is built for the call; the workspace is the context's own (freed by
+ * wm_ctx_destroy); the registration state and the outlier and ground workspaces are not touched. */
+int wm_cluster_extract(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                       const wm_cluster_params *p,
+                       int32_t *labels_out /* NULL ok: n entries */,
+                       int32_t *indices_out, size_t cap,              /* the clusters' members, back to back */
+                       uint32_t *offsets_out, size_t cap_clusters,    /* cap_clusters + 1 entries */
+                       int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

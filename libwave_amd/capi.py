@@ -133,6 +133,19 @@ WM_OUTLIER_STATISTICAL, WM_OUTLIER_RADIUS = 0, 1
 WM_OUTLIER_NONE, WM_OUTLIER_INLIER, WM_OUTLIER_OUTLIER = 0, 1, 2
 WM_OUTLIER_MAX_MEAN_K = 31  # the k-NN search keeps lists of 32, the point itself among them
 
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("tolerance", C.c_double), ("min_cluster_size", C.c_int), ("max_cluster_size", C.c_int)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("n_components", C.c_size_t), ("n_clusters", C.c_size_t),
+                ("n_clustered", C.c_size_t), ("largest", C.c_size_t), ("kernel_ms", C.c_float)]
+
+
+WM_CLUSTER_NONE, WM_CLUSTER_REJECTED = -1, -2
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -280,6 +293,11 @@ def lib():
         L.wm_outlier_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(OutlierParams),
                                         C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(OutlierStats)]
+        L.wm_cluster_default_params.argtypes = [C.POINTER(ClusterParams)]
+        L.wm_cluster_default_params.restype = None
+        L.wm_cluster_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(ClusterParams),
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
         _LIB = L
     return _LIB
 
@@ -343,6 +361,17 @@ def outlier_params(params=None, **kw):
     """wm_outlier_params from PCL's defaults (wm_outlier_default_params), a dict of field values and keywords."""
     p = OutlierParams()
     lib().wm_outlier_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def cluster_params(params=None, **kw):
+    """wm_cluster_params from PCL's defaults (wm_cluster_default_params), a dict of field values and keywords."""
+    p = ClusterParams()
+    lib().wm_cluster_default_params(C.byref(p))
     for k, v in dict(params or {}, **kw).items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -598,6 +627,46 @@ class Context:
             out["labels"] = labels[:n]
             out["mean_dist" if stat else "counts"] = extra[:n] if extra is not None else None
         out.update({k: getattr(st, k) for k, _ in OutlierStats._fields_})
+        return out
+
+    def cluster_extract(self, cloud, params=None, labels=True, out_mem=None, **kw):
+        """pcl::EuclideanClusterExtraction on the device (wm_cluster_extract) -> dict: rc, labels (n,) int32 (the
+        cluster's rank, WM_CLUSTER_REJECTED or WM_CLUSTER_NONE; None with labels=False), indices (the clusters'
+        members back to back, int32), offsets (n_clusters + 1,) uint32 -- cluster c is indices[offsets[c]:offsets[c + 1]]
+        -- n_clusters, n_out and the fields of wm_cluster_stats.  `cloud`: float32 (n, 3|4) numpy array or a HIP torch
+        tensor.  out_mem: where the three arrays are written, WM_MEM_HOST (numpy arrays) or WM_MEM_DEVICE (torch
+        tensors); by default where the cloud lives.  `params`: a ClusterParams, a dict of its fields, or None (PCL's
+        defaults: the tolerance must then come as a keyword); keywords override fields."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        if isinstance(params, ClusterParams):
+            params = {k: getattr(params, k) for k, _ in ClusterParams._fields_}
+        p = cluster_params(params, **kw)
+        out_mem = mem if out_mem is None else out_mem
+        m, k = C.c_size_t(0), C.c_size_t(0)
+        st = ClusterStats()
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            lab = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if labels else None
+            idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            off = torch.zeros(n + 1, dtype=torch.int32, device=dev)  # (torch has no uint32 arithmetic: the bits are)
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            lab = np.empty(max(n, 1), np.int32) if labels else None
+            idx = np.empty(max(n, 1), np.int32)
+            off = np.zeros(n + 1, np.uint32)
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = self._check(lib().wm_cluster_extract(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), addr(lab), addr(idx),
+                                                  n, addr(off), n, out_mem, C.byref(k), C.byref(m), C.byref(st)),
+                         "wm_cluster_extract")
+        out = dict(rc=rc, labels=lab[:n] if labels else None, indices=idx[:m.value], offsets=off[:k.value + 1],
+                   n_clusters=k.value, n_out=m.value)
+        out.update({f: getattr(st, f) for f, _ in ClusterStats._fields_})
         return out
 
     def ground_segment_batch(self, clouds, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING, points=False):

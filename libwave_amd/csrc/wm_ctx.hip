@@ -233,6 +233,8 @@ const Option kOptions[] = {
     {"gicp_profile", "WM_GICP_PROFILE", &wm_ctx::gicp_profile, nullptr, kIntMin, kIntMax, kFlag},
     // outlier removal (wm_outlier.hip)
     {"outlier_cell_div", "WM_TUNE_OUTLIER_CELL_DIV", nullptr, &wm_ctx::tune_outlier_cell_div, 0.5, 8, 0},
+    // cluster extraction (wm_cluster.hip)
+    {"cluster_cell_div", "WM_TUNE_CLUSTER_CELL_DIV", nullptr, &wm_ctx::tune_cluster_cell_div, 0.5, 8, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
     {"ndt_dense", "WM_TUNE_NDT_DENSE", &wm_ctx::tune_ndt_dense, nullptr, kIntMin, kIntMax, 0},
@@ -323,6 +325,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     batch_voxel_release(ctx);
     ground_release(ctx);
     outlier_release(ctx);
+    cluster_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

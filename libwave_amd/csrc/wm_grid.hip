@@ -439,6 +439,34 @@ int build_grid_level(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, f
     return WM_OK;
 }
 
+static uint64_t cells_of(const Bbox &bb, float h) {  // (build_grid_level's lattice)
+    uint64_t c = 1;
+    for (int d = 0; d < 3; ++d) c *= (uint64_t) floor(((double) bb.hi[d] - bb.lo[d]) / h) + 1;
+    return c;
+}
+
+// The grid of one call over an arbitrary packed cloud (wm_outlier_filter, wm_cluster_extract).  The automatic cell is
+// source_grid's (wm_gicp.hip): 1.5 x the cube root of the box's volume per point, rebuilt once when the occupied
+// cells hold more than 6 or fewer than 1.5 points on average.  A fixed-radius search's box [q - r, q + r] must span a
+// bounded number of rows, so its cell is never smaller than `floor_h` (r / 2 by default: at most 6 x 6 rows of at most
+// 6 cells); 0 for a search without a radius.
+int build_call_grid(wm_ctx *ctx, const float4 *pts, size_t n, size_t n_finite, const Bbox &bb, float floor_h,
+                    GridLevel *grid) {
+    double vol = 1;
+    for (int d = 0; d < 3; ++d) vol *= fmax((double) bb.hi[d] - bb.lo[d], 1e-3);
+    float h = fmaxf((float) fmax(cbrt(vol / (double) n_finite) * 1.5, 1e-4), floor_h);
+    const uint64_t cell_cap = ((uint64_t) 1 << 26) + 8 * (uint64_t) n;  // (a lattice far beyond the points pays for nothing)
+    while (cells_of(bb, h) > cell_cap) h *= 1.26f;
+    double occ = 0;
+    WM_TRY(build_grid_level(ctx, pts, n, bb, h, grid, &occ));
+    if (occ > 6.0 || (occ > 0 && occ < 1.5)) {
+        float h2 = fmaxf((float) (h * sqrt(3.0 / occ)), floor_h);
+        while (cells_of(bb, h2) > cell_cap) h2 *= 1.26f;
+        if (h2 != h) WM_TRY(build_grid_level(ctx, pts, n, bb, h2, grid, nullptr));
+    }
+    return WM_OK;
+}
+
 // Source ordering: stable radix sort of (Morton cell code, original index) pairs, then a
 // gather.  Stable => points of one Morton cell keep ascending original index, so every
 // downstream sum over the source runs in a reproducible order.  Non-finite points get the

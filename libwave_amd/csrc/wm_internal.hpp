@@ -298,6 +298,8 @@ struct wm_ctx {
     int gicp_profile = 0;        // HIP events around every objective evaluation (fdf_kernel_ms)
     // outlier removal (wm_outlier.hip)
     float tune_outlier_cell_div = 2.f;  // the radius filter's grid cell is at least radius / this (0.5 ... 8)
+    // cluster extraction (wm_cluster.hip)
+    float tune_cluster_cell_div = 2.f;  // the clustering's grid cell is at least tolerance / this (0.5 ... 8)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_ndt_dense = 2;      // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice
@@ -327,6 +329,7 @@ struct wm_ctx {
     void *batch_voxel = nullptr;            // wm_batch.hip: buffers of the batched voxel filter
     void *ground = nullptr;                 // wm_ground.hip: the ground filter's workspace (its own, shared with nothing)
     void *outlier = nullptr;                // wm_outlier.hip: the outlier filters' workspace (its own as well)
+    void *cluster = nullptr;                // wm_cluster.hip: the cluster extraction's workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -549,6 +552,9 @@ int launch_bbox(wm_ctx *ctx, const float4 *pts, size_t n, float *partials_dev, u
 void finish_bbox(const float *partials_host, unsigned blocks, Bbox *out, size_t *n_valid);
 int build_grid_level(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, float h,
                      GridLevel *lvl, double *avg_occupancy);
+// one call's grid over an arbitrary packed cloud: the automatic cell, never below floor_h (see wm_grid.hip)
+int build_call_grid(wm_ctx *ctx, const float4 *pts, size_t n, size_t n_finite, const Bbox &bb, float floor_h,
+                    GridLevel *grid);
 int morton_sort(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, size_t n_valid,
                 float4 *out);
 int ensure_levels(wm_ctx *ctx, double max_corr);
@@ -632,6 +638,9 @@ void ground_release(wm_ctx *ctx);
 
 // ---- wm_outlier.hip
 void outlier_release(wm_ctx *ctx);
+
+// ---- wm_cluster.hip
+void cluster_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0

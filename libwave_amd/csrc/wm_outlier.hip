@@ -24,7 +24,7 @@
 //                order: the cell sort's order inside a cell is the atomics' arrival order and must not reach a sum)
 //   radius       k_outlier_radius<EXACT> (one lane per query over the rows of the box [q - r, q + r])
 //   both         k_outlier_label, exclusive_scan, k_outlier_compact (kept indices in ascending input order).
-#include "wm_gicp_dev.hpp"
+#include "wm_radius_walk.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -117,11 +117,9 @@ __global__ void __launch_bounds__(64)
 }
 
 // ------------------------------------------------------------------ radius: neighbours within r
-// One lane per query (grid order, result under .w).  The box of cells covering [q - r, q + r] is resolved a batch of
-// kKnnRows rows at a time, as knn_search resolves its rows: a row of x-adjacent cells is ONE contiguous run of the
-// cell-sorted points, the batch's cell_start look-ups are issued together, the non-empty runs go to the lane's column
-// of `runs` (LDS) and are walked in one flat loop with the next candidate's load in flight.  hits counts d2 < r2, the
-// query itself among them (d2 = 0) whenever r2 > 0; the count written is the OTHER points'.
+// One lane per query (grid order, result under .w) over the rows of the box of cells covering [q - r, q + r]:
+// radius_walk (wm_radius_walk.hpp, shared with k_cluster_link).  hits counts d2 < r2, the query itself among them
+// (d2 = 0) whenever r2 > 0; the count written is the OTHER points'.
 // EXACT: the count is exact.  Otherwise a lane stops once it has seen `stop` hits (min_neighbors + 1, itself
 // included): what it writes then is >= min_neighbors, which is all the labelling asks.
 template <bool EXACT>
@@ -131,58 +129,11 @@ __global__ void __launch_bounds__(kOutBlock)
     const unsigned i = blockIdx.x * kOutBlock + threadIdx.x;
     if (i >= n) return;
     const float4 q = g.pts[i];
-    uint2 *runs = s_runs;
-    const unsigned lane_col = threadIdx.x;
-    const float fx = (q.x - g.ox) * g.inv_h, fy = (q.y - g.oy) * g.inv_h, fz = (q.z - g.oz) * g.inv_h;
-    const float rc = r_cells + g.slack;
-    // (clamped as floats: r may exceed what an int holds)
-    const int xa = (int) fmaxf(floorf(fx - rc), 0.f), xb = (int) fminf(floorf(fx + rc), (float) (g.nx - 1));
-    const int ya = (int) fmaxf(floorf(fy - rc), 0.f), yb = (int) fminf(floorf(fy + rc), (float) (g.ny - 1));
-    const int za = (int) fmaxf(floorf(fz - rc), 0.f), zb = (int) fminf(floorf(fz + rc), (float) (g.nz - 1));
     unsigned hits = 0;
-    const bool any = xa <= xb && ya <= yb && za <= zb;
-    int yy = ya, zz = any ? za : zb + 1;  // row cursor; zz > zb = past the last row
-    while (zz <= zb && (EXACT || hits < stop)) {
-        int n_runs = 0;
-        unsigned rs[kKnnRows], re[kKnnRows];
-#pragma unroll
-        for (int u = 0; u < kKnnRows; ++u) {
-            const bool live = zz <= zb;
-            const size_t base = ((size_t) (live ? zz : za) * g.ny + (live ? yy : ya)) * g.nx;
-            rs[u] = g.cell_start[base + xa];
-            re[u] = live ? g.cell_start[base + xb + 1] : 0u;  // dead row: e <= s
-            if (++yy > yb) {
-                yy = ya;
-                ++zz;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kKnnRows; ++u)
-            if (re[u] > rs[u]) {
-                runs[n_runs * kOutBlock + lane_col] = make_uint2(rs[u], re[u]);
-                ++n_runs;
-            }
-        if (n_runs == 0) continue;
-        int ri = 0;
-        const uint2 r0 = runs[lane_col];
-        unsigned j = r0.x, e = r0.y;
-        float4 t = g.pts[j];
-        for (;;) {
-            bool more = true;
-            if (++j == e) {
-                more = ++ri < n_runs;
-                if (more) {
-                    const uint2 rn = runs[ri * kOutBlock + lane_col];
-                    j = rn.x;
-                    e = rn.y;
-                }
-            }
-            const float4 tn = g.pts[more ? j : r0.x];  // (a lane at its end reads a line it has had already)
-            hits += g_d2(q.x, q.y, q.z, t) < r2 ? 1u : 0u;
-            if (!more || (!EXACT && hits >= stop)) break;
-            t = tn;
-        }
-    }
+    radius_walk<!EXACT>(g, q, r_cells, s_runs, threadIdx.x, kOutBlock, [&](unsigned, const float4 &t) {
+        hits += g_d2(q.x, q.y, q.z, t) < r2 ? 1u : 0u;
+        return !EXACT && hits >= stop;
+    });
     const unsigned self = r2 > 0.f ? 1u : 0u;
     count_out[__float_as_uint(q.w)] = (int) (hits - (hits >= self ? self : 0u));
 }
@@ -258,33 +209,6 @@ int launch_mean_dist_k(wm_ctx *ctx, const GridDev &g, size_t n, int k, float *di
     if (k <= 20) return launch_mean_dist<20>(ctx, g, n, k, dist);
     if (k <= 24) return launch_mean_dist<24>(ctx, g, n, k, dist);
     return launch_mean_dist<32>(ctx, g, n, k, dist);
-}
-
-uint64_t cells_of(const Bbox &bb, float h) {  // (build_grid_level's lattice)
-    uint64_t c = 1;
-    for (int d = 0; d < 3; ++d) c *= (uint64_t) floor(((double) bb.hi[d] - bb.lo[d]) / h) + 1;
-    return c;
-}
-
-// The call's grid.  The automatic cell is source_grid's (wm_gicp.hip): 1.5 x the cube root of the box's volume per
-// point, rebuilt once when the occupied cells hold more than 6 or fewer than 1.5 points on average.  The radius
-// filter's box [q - r, q + r] must span a bounded number of rows, so its cell is never smaller than `floor_h` =
-// radius / outlier_cell_div (2: at most 6 x 6 rows of at most 6 cells; DESIGN.md 4.8 has the measurements).
-int outlier_grid(wm_ctx *ctx, OutlierWs &w, size_t n, size_t n_finite, const Bbox &bb, float floor_h) {
-    double vol = 1;
-    for (int d = 0; d < 3; ++d) vol *= fmax((double) bb.hi[d] - bb.lo[d], 1e-3);
-    float h = fmaxf((float) fmax(cbrt(vol / (double) n_finite) * 1.5, 1e-4), floor_h);
-    const uint64_t cell_cap = ((uint64_t) 1 << 26) + 8 * (uint64_t) n;  // (a lattice far beyond the points pays for nothing)
-    while (cells_of(bb, h) > cell_cap) h *= 1.26f;
-    double occ = 0;
-    const float4 *pts = w.pts.as<float4>();
-    WM_TRY(build_grid_level(ctx, pts, n, bb, h, &w.grid, &occ));
-    if (occ > 6.0 || (occ > 0 && occ < 1.5)) {
-        float h2 = fmaxf((float) (h * sqrt(3.0 / occ)), floor_h);
-        while (cells_of(bb, h2) > cell_cap) h2 *= 1.26f;
-        if (h2 != h) WM_TRY(build_grid_level(ctx, pts, n, bb, h2, &w.grid, nullptr));
-    }
-    return WM_OK;
 }
 
 bool outlier_params_ok(const wm_outlier_params *p) {
@@ -392,7 +316,9 @@ int wm_outlier_filter(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int
         rf = sqrtf(r2) * 1.0001f;  // (a point with float d2 < r2 lies within this of the query)
     }
     const float div = ctx->tune_outlier_cell_div;
-    WM_TRY(outlier_grid(ctx, w, n, n_finite, bb, stat ? 0.f : fminf((float) p->radius, 1.0e30f) / div));
+    // (the radius filter's box [q - r, q + r] must span a bounded number of rows: DESIGN.md 4.8 has the measurements)
+    WM_TRY(build_call_grid(ctx, w.pts.as<float4>(), n, n_finite, bb, stat ? 0.f : fminf((float) p->radius, 1.0e30f) / div,
+                           &w.grid));
     const GridDev &g = w.grid.d;
 
     WM_HIP(ctx, hipMemsetAsync(w.res.p, 0, 4 * sizeof(double), st));
