@@ -47,6 +47,10 @@ void clusterRelease(wm_ctx *&ctx);
 // false (after a LOG_ERROR, `out` empty) on bad parameters or a device error
 bool clusterExtract(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride,
                     const ClusterExtractionParams &params, std::vector<pcl::PointIndices> &out);
+// a queue of clouds in ONE call (wm_cluster_extract_batch): pts[k] / n[k] are cloud k's records; out[k] its clusters
+bool clusterExtractBatch(wm_ctx *&ctx, int device, const std::vector<const void *> &pts, const std::vector<size_t> &n,
+                         size_t stride, const ClusterExtractionParams &params,
+                         std::vector<std::vector<pcl::PointIndices>> &out);
 }  // namespace detail
 
 template <typename PointT>
@@ -73,6 +77,11 @@ class EuclideanClusterExtraction {
 
     // the clusters of input_ (wm_cluster_extract), largest first, each one's indices ascending
     void extract(std::vector<pcl::PointIndices> &clusters);
+
+    // A queue of clouds in one device call (wm_cluster_extract_batch): clusters[k] is what setInputCloud(clouds[k]);
+    // extract(...) gives.  The input cloud of the object is not used and not changed.  A null pointer among the
+    // clouds, bad parameters or a device error: a LOG_ERROR and `clusters` empty.
+    void extractBatch(const std::vector<PointCloudConstPtr> &clouds, std::vector<std::vector<pcl::PointIndices>> &clusters);
 
  private:
     PointCloudConstPtr input_;

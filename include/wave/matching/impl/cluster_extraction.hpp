@@ -45,6 +45,26 @@ void EuclideanClusterExtraction<PointT>::extract(std::vector<pcl::PointIndices> 
         clusters.clear();
 }
 
+template <typename PointT>
+void EuclideanClusterExtraction<PointT>::extractBatch(const std::vector<PointCloudConstPtr> &clouds,
+                                                      std::vector<std::vector<pcl::PointIndices>> &clusters) {
+    static_assert(sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) % 4 == 0,
+                  "EuclideanClusterExtraction: a point type whose first three floats are x, y, z");
+    clusters.clear();
+    std::vector<const void *> pts(clouds.size(), nullptr);
+    std::vector<size_t> n(clouds.size(), 0);
+    for (size_t k = 0; k < clouds.size(); ++k) {
+        if (clouds[k]) {
+            n[k] = clouds[k]->points.size();
+            pts[k] = n[k] ? clouds[k]->points.data() : nullptr;
+        } else {
+            n[k] = static_cast<size_t>(-1);  // (detail::clusterExtractBatch logs it)
+        }
+    }
+    if (!detail::clusterExtractBatch(this->ctx, this->device, pts, n, sizeof(PointT), this->params, clusters))
+        clusters.clear();
+}
+
 }  // namespace wave
 
 // PCL_INSTANTIATE_EuclideanClusterExtraction(MyPoint) in one source file of a program precompiles the class for MyPoint

@@ -848,6 +848,45 @@ int wm_cluster_extract(wm_ctx *ctx, const void *pts, size_t n, size_t stride_byt
                        uint32_t *offsets_out, size_t cap_clusters,    /* cap_clusters + 1 entries */
                        int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats /* NULL ok */);
 
+/* A queue of scans in one device call: the same kernels with a scan dimension, one `p`, one stride and one `mem` for
+ * the batch (as wm_ground_segment_batch).  The clusters of the batch are numbered scan after scan: scan k's are
+ * [cluster_first[k], cluster_first[k + 1]), cluster_first[n_scans] is their number in all, and cluster g is
+ * indices_out[offsets_out[g] .. offsets_out[g + 1]) -- indices inside its scan.  labels_out: the scans' n entries one
+ * after the other, a cluster's rank INSIDE its scan, WM_CLUSTER_REJECTED or WM_CLUSTER_NONE.  points_out: per entry
+ * of indices_out the input point's x y z, bit for bit, in records of out_stride bytes (>= 12, a multiple of 4; the
+ * bytes behind z are zero) -- wm_ground_segment_batch's rules, and what wm_icp_batch_match takes as it is.  out_mem
+ * says where labels_out, indices_out, points_out and offsets_out live; cluster_first (n_scans + 1 entries), n_out (the
+ * kept points of all scans) and stats (n_scans entries) are host memory; kernel_ms, here and in every stats[k], is
+ * the batch's.
+ * For every scan k its labels, its indices, its offsets less offsets_out[cluster_first[k]] and stats[k] (but
+ * kernel_ms) EQUAL what wm_cluster_extract returns for that scan alone.  Empty scans and scans without a finite point
+ * have empty slices; n_scans == 0, or no point in any scan: WM_OK and no device touched (offsets_out[0] = 0 is then
+ * written only where out_mem is WM_MEM_HOST).  More kept points than `cap` or more clusters than `cap_clusters`:
+ * WM_ERR_ARG with *n_out and cluster_first the true counts, the first `cap` indices and points and the first
+ * cap_clusters + 1 offsets written, the offsets clamped to `cap`.  Argument errors, found before a device is touched:
+ * wm_cluster_extract's, a null scans / cluster_first, a scan with a null pts and n > 0, a bad out_stride with
+ * points_out, and a batch beyond the limits below.  A batch of one scan is the single call.
+ * Each scan has a lattice of its own; where the single call allows a scan 2^26 + 8 n cells, a batch allows scan k
+ * 8 n_k + max(2^26 / n_scans, 4096): one 2^26 for the whole batch.  Coarser cells change no output.
+ * The workspace is the one of wm_cluster_extract. */
+typedef struct { const void *pts; size_t n; } wm_cluster_scan;
+#define WM_CLUSTER_BATCH_MAX_POINTS 0x7FFFFFF0ull /* the scans' points in all, at most */
+#define WM_CLUSTER_BATCH_MAX_SCANS 0x1000000ull   /* n_scans at most */
+/* the kept clusters are ordered by ONE 64-bit key (scan, size, smallest member index):
+ * bits(n_scans - 1) + 2 * bits(the largest scan's n) <= WM_CLUSTER_BATCH_KEY_BITS, bits(v) = the binary digits of v
+ * (4 096 scans of 2^20 points: 12 + 2 * 21) */
+#define WM_CLUSTER_BATCH_KEY_BITS 64
+int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_scans, size_t stride_bytes, int mem,
+                             const wm_cluster_params *p,
+                             int32_t *labels_out /* NULL ok: the scans' n entries one after the other */,
+                             int32_t *indices_out, size_t cap,
+                             void *points_out /* NULL ok */, size_t out_stride,
+                             uint32_t *offsets_out, size_t cap_clusters /* cap_clusters + 1 entries */,
+                             int out_mem,
+                             size_t *cluster_first /* host, n_scans + 1 entries */,
+                             size_t *n_out, wm_cluster_stats *stats /* NULL ok: n_scans entries */,
+                             float *kernel_ms /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -144,7 +144,14 @@ class ClusterStats(C.Structure):
                 ("n_clustered", C.c_size_t), ("largest", C.c_size_t), ("kernel_ms", C.c_float)]
 
 
+class ClusterScan(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_size_t)]
+
+
 WM_CLUSTER_NONE, WM_CLUSTER_REJECTED = -1, -2
+WM_CLUSTER_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of a cluster_extract_batch's scans in all
+WM_CLUSTER_BATCH_MAX_SCANS = 0x1000000
+WM_CLUSTER_BATCH_KEY_BITS = 64  # bits(n_scans - 1) + 2 * bits(the largest scan's n), at most
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -298,6 +305,10 @@ def lib():
         L.wm_cluster_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(ClusterParams),
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
+        L.wm_cluster_extract_batch.argtypes = [C.c_void_p, C.POINTER(ClusterScan), C.c_int, C.c_size_t, C.c_int,
+                                               C.POINTER(ClusterParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_size_t), C.POINTER(ClusterStats), C.POINTER(C.c_float)]
         _LIB = L
     return _LIB
 
@@ -668,6 +679,76 @@ class Context:
                    n_clusters=k.value, n_out=m.value)
         out.update({f: getattr(st, f) for f, _ in ClusterStats._fields_})
         return out
+
+    def cluster_extract_batch(self, clouds, params=None, labels=True, points=False, out_mem=None, **kw):
+        """cluster_extract for a queue of scans in one device call (wm_cluster_extract_batch) -> one dict per scan with
+        the keys of cluster_extract, each EQUAL to cluster_extract's for that scan alone (offsets start at 0, indices
+        and labels are the scan's own; kernel_ms is the batch's).  `clouds`: float32 (n, 3|4) numpy arrays or HIP torch
+        tensors (separate allocations are fine), all of one kind; one `params` for the batch.  out_mem as in
+        cluster_extract.  points=True: -> (that list, kept, offsets) with `kept` the members' points of all scans in
+        the order of the indices, (m, 3|4) float32, scan k's at kept[offsets[k]:offsets[k + 1]] -- in device memory a
+        tensor whose slices icp_batch_match takes as they are."""
+        n_scans = len(clouds)
+        if isinstance(params, ClusterParams):
+            params = {k: getattr(params, k) for k, _ in ClusterParams._fields_}
+        p = cluster_params(params, **kw)
+        scans = (ClusterScan * max(n_scans, 1))()
+        alive, stride, mem, sizes = [], None, None, []
+        for k, cloud in enumerate(clouds):
+            ptr, n, sk, mk, a = _cloud_arg(cloud)
+            assert stride in (None, sk) and mem in (None, mk), "the scans of a batch share one layout and one memory"
+            stride, mem = sk, mk
+            alive.append(a)
+            scans[k].pts, scans[k].n = ptr, n
+            sizes.append(n)
+        stride, mem = stride or 12, WM_MEM_HOST if mem is None else mem
+        out_mem = mem if out_mem is None else out_mem
+        total = sum(sizes)
+        first = (C.c_size_t * (n_scans + 1))()
+        st = (ClusterStats * max(n_scans, 1))()
+        m, ms = C.c_size_t(0), C.c_float(0)
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = clouds[0].device if mem == WM_MEM_DEVICE and n_scans else "cuda:%d" % self.device
+            lab = torch.empty(max(total, 1), dtype=torch.int32, device=dev) if labels else None
+            idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+            off = torch.zeros(total + 1, dtype=torch.int32, device=dev)  # (torch has no uint32 arithmetic: the bits are)
+            kept = torch.empty((max(total, 1), stride // 4), dtype=torch.float32, device=dev) if points else None
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            lab = np.empty(max(total, 1), np.int32) if labels else None
+            idx = np.empty(max(total, 1), np.int32)
+            off = np.zeros(total + 1, np.uint32)
+            kept = np.empty((max(total, 1), stride // 4), np.float32) if points else None
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = self._check(lib().wm_cluster_extract_batch(self._h, scans, n_scans, stride, mem, C.byref(p), addr(lab), addr(idx),
+                                                        total, addr(kept), stride if points else 0, addr(off), total, out_mem,
+                                                        first, C.byref(m), st, C.byref(ms)), "wm_cluster_extract_batch")
+        first = [int(v) for v in first]
+        # the scans' own offsets (each from 0) are cut on the host: one small copy down, and one up for device outputs
+        h_off = off[:first[-1] + 1].cpu().numpy().view(np.uint32) if out_mem == WM_MEM_DEVICE else off
+        own = [h_off[first[k]:first[k + 1] + 1] - h_off[first[k]] for k in range(n_scans)]
+        if out_mem == WM_MEM_DEVICE and n_scans:
+            flat = torch.from_numpy(np.concatenate(own).view(np.int32)).to(dev)
+            ends = np.cumsum([len(o) for o in own])
+            own = [flat[e - len(o):e] for o, e in zip(own, ends)]
+        out, at, pt_offs = [], 0, [0]
+        for k in range(n_scans):
+            ia, ib = int(h_off[first[k]]), int(h_off[first[k + 1]])
+            d = dict(rc=rc, labels=lab[at:at + sizes[k]] if labels else None, indices=idx[ia:ib], offsets=own[k],
+                     n_clusters=first[k + 1] - first[k], n_out=ib - ia)
+            d.update({f: getattr(st[k], f) for f, _ in ClusterStats._fields_})
+            out.append(d)
+            at += sizes[k]
+            pt_offs.append(ib)
+        if not points:
+            return out
+        return out, kept[:m.value], np.array(pt_offs, np.int64)
 
     def ground_segment_batch(self, clouds, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING, points=False):
         """The filter for a queue of scans in one device call (wm_ground_segment_batch) -> [(labels, indices,

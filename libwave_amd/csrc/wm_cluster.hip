@@ -1,6 +1,7 @@
 // wm_cluster.hip -- Euclidean cluster extraction on the device: pcl::EuclideanClusterExtraction as one cloud-in /
 // clusters-out call (wm_cluster_extract), shaped like wm_outlier_filter: the call packs the cloud, builds a cell-sorted
-// grid over it for this call alone, and works in a workspace of its own on the context.
+// grid over it for this call alone, and works in a workspace of its own on the context.  wm_cluster_extract_batch is
+// the same for a queue of scans: one set of kernels with a scan dimension, as wm_ground_segment_batch.
 //
 // The rule (written from PCL 1.8 segmentation/impl/extract_clusters.hpp; PCL is not linked, the checker is
 // tests/cluster_reference.py): two different finite points are joined iff d2 < r2 (strict, as FLANN's radius set),
@@ -21,14 +22,24 @@
 // A root is whatever grid position is the smallest of its component -- inside a cell that is the arrival order of the
 // grid's atomics (see k_outlier_moments' note) -- so a root's number never reaches an output: the order of the
 // clusters comes from (size, smallest caller index) alone.
+//
+// A batch (ClScan: a scan's row of the device table; tab == nullptr is the single call, its scan handed over by
+// value): the scans' points stand one after the other ("batch positions", scan-major), each scan has a lattice of its
+// own whose cells are numbered scan after scan, so one count, one exclusive scan and one scatter give ONE cell-sorted
+// array, scan-major again ("grid positions").  A scan's GridDev points at its own slice of cell_start and at the
+// shared array, so a walk never meets a point of another scan, and the union-find, the counters, the two sorts and
+// the outputs run over the whole batch at once: the sort key of a kept root leads with its scan, a member's with its
+// cluster's batch-wide rank.  The number of launches and host waits does not depend on the number of scans.
 #include <limits.h>
 #include <string.h>  // (before rocPRIM's headers, which call memset)
 
 #include "wm_radius_walk.hpp"
 #include "wm_sort.hpp"
+#include "wm_stage.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 namespace wm {
 
@@ -37,6 +48,156 @@ namespace {
 constexpr int kLinkBlock = 64;  // queries (threads) of a link workgroup: one wave, as k_outlier_radius
 
 #define WM_UF_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+struct ClScan {  // one scan of a batch
+    const unsigned char *raw;  // its records (device memory)
+    unsigned n, off;           // points; its first batch position
+    unsigned blk0;             // its first workgroup of the kernels over batch positions (kBlock points each)
+    unsigned nf, g0;           // finite points; its first grid position
+    unsigned lblk0;            // its first workgroup of k_cluster_link
+    unsigned long long cell0;  // its first cell
+    GridDev g;                 // its lattice: cell_start = the scan's first cell, pts = the batch's cell-sorted array
+};
+
+// The last scan whose `field` is at or below x.  Scans without points (or without finite points, or without
+// workgroups) share their value with the scan behind them, so the last one found is the one that owns x.
+template <class Field>
+__device__ __forceinline__ unsigned cl_find(const ClScan *__restrict__ tab, unsigned S, unsigned x, Field field) {
+    unsigned k = 0, hi = S;
+    while (hi - k > 1u) {
+        const unsigned mid = (k + hi) >> 1;
+        if (field(tab[mid]) <= x) k = mid;
+        else hi = mid;
+    }
+    return k;
+}
+__device__ __forceinline__ unsigned cl_by_block(const ClScan *tab, unsigned S, unsigned b) {
+    return cl_find(tab, S, b, [](const ClScan &s) { return s.blk0; });
+}
+__device__ __forceinline__ unsigned cl_by_grid(const ClScan *tab, unsigned S, unsigned x) {
+    return cl_find(tab, S, x, [](const ClScan &s) { return s.g0; });
+}
+__device__ __forceinline__ unsigned cl_by_point(const ClScan *tab, unsigned S, unsigned p) {
+    return cl_find(tab, S, p, [](const ClScan &s) { return s.off; });
+}
+
+// float -> unsigned whose unsigned order is the float order (-0.0 canonicalised to +0.0 first)
+__device__ __forceinline__ unsigned cl_orderable(float z) {
+    const unsigned b = __float_as_uint(z == 0.f ? 0.f : z);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// ------------------------------------------------------------------ the front of a batch: pack, boxes, the grid
+// k_pack's conversion into batch positions (.w = the batch position: the scan and the caller's index are recovered
+// from it by the table), and per scan the box and the finite count -- bb: [3 S] minima, [3 S] maxima (orderable),
+// [S] counts.  Minima, maxima and integer sums: the order of the atomics does not matter.
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_pack(const ClScan *__restrict__ tab, unsigned S, size_t stride, float4 *__restrict__ out, unsigned *bb) {
+    __shared__ unsigned s_lo[kBlock / 64][3], s_hi[kBlock / 64][3], s_cnt[kBlock / 64];
+    const unsigned k = cl_by_block(tab, S, blockIdx.x);
+    const ClScan me = tab[k];
+    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
+    unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, cnt = 0u;
+    if (i < me.n) {
+        const float *q = reinterpret_cast<const float *>(me.raw + (size_t) i * stride);
+        float x = q[0], y = q[1], z = q[2];
+        if (isfinite(x) && isfinite(y) && isfinite(z)) {
+            lo[0] = hi[0] = cl_orderable(x);
+            lo[1] = hi[1] = cl_orderable(y);
+            lo[2] = hi[2] = cl_orderable(z);
+            cnt = 1u;
+        } else {
+            x = y = z = __builtin_nanf("");
+        }
+        out[me.off + i] = make_float4(x, y, z, __uint_as_float(me.off + i));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        for (int d = 0; d < 3; ++d) {
+            lo[d] = min(lo[d], (unsigned) __shfl_down(lo[d], off));
+            hi[d] = max(hi[d], (unsigned) __shfl_down(hi[d], off));
+        }
+        cnt += __shfl_down(cnt, off);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        for (int d = 0; d < 3; ++d) {
+            s_lo[wave][d] = lo[d];
+            s_hi[wave][d] = hi[d];
+        }
+        s_cnt[wave] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; ++w) {
+            for (int d = 0; d < 3; ++d) {
+                lo[d] = min(lo[d], s_lo[w][d]);
+                hi[d] = max(hi[d], s_hi[w][d]);
+            }
+            cnt += s_cnt[w];
+        }
+        if (cnt) {
+            for (int d = 0; d < 3; ++d) {
+                atomicMin(&bb[3u * k + d], lo[d]);
+                atomicMax(&bb[3u * S + 3u * k + d], hi[d]);
+            }
+            atomicAdd(&bb[6u * S + k], cnt);
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned cl_cell(const GridDev &g, const float4 &p) {  // (wm_grid.hip: LinearKey)
+    int cx = (int) floorf((p.x - g.ox) * g.inv_h);
+    int cy = (int) floorf((p.y - g.oy) * g.inv_h);
+    int cz = (int) floorf((p.z - g.oz) * g.inv_h);
+    cx = min(max(cx, 0), g.nx - 1);
+    cy = min(max(cy, 0), g.ny - 1);
+    cz = min(max(cz, 0), g.nz - 1);
+    return (unsigned) ((cz * g.ny + cy) * g.nx + cx);
+}
+
+// k_count of wm_grid.hip with the scan's lattice and its first cell; the lane that finds a cell empty counts it as
+// occupied (occ[k]: what build_call_grid's occupancy check fetches, here for every scan at once)
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_count(const ClScan *__restrict__ tab, unsigned S, const float4 *__restrict__ pts, unsigned *__restrict__ cell_of,
+                    unsigned *__restrict__ rank_of, unsigned *counts, unsigned *occ) {
+    const unsigned k = cl_by_block(tab, S, blockIdx.x);
+    const ClScan me = tab[k];
+    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
+    unsigned first = 0u;
+    if (i < me.n) {
+        const float4 p = pts[me.off + i];
+        unsigned c = kNoIdx, r = 0u;
+        if (p.x == p.x) {
+            c = cl_cell(me.g, p);
+            r = atomicAdd(&counts[me.cell0 + c], 1u);
+            first = r == 0u ? 1u : 0u;
+        }
+        cell_of[me.off + i] = c;
+        rank_of[me.off + i] = r;
+    }
+    for (int off = 32; off > 0; off >>= 1) first += __shfl_down(first, off);
+    if ((threadIdx.x & 63) == 0 && first) atomicAdd(&occ[k], first);
+}
+
+// k_scatter of wm_grid.hip: the batch's cell-sorted array and the four NaN entries behind its last point
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_scatter(const ClScan *__restrict__ tab, unsigned S, const float4 *__restrict__ pts,
+                      const unsigned *__restrict__ cell_of, const unsigned *__restrict__ rank_of,
+                      const unsigned *__restrict__ cell_start, float4 *__restrict__ out, size_t ncells) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const unsigned end = cell_start[ncells];
+        const float nanv = __builtin_nanf("");
+#pragma unroll
+        for (int u = 0; u < 4; ++u) out[end + u] = make_float4(nanv, nanv, nanv, __uint_as_float(kNoIdx));
+    }
+    const unsigned k = cl_by_block(tab, S, blockIdx.x);
+    const ClScan me = tab[k];
+    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
+    if (i >= me.n) return;
+    const unsigned c = cell_of[me.off + i];
+    if (c == kNoIdx) return;
+    out[cell_start[me.cell0 + c] + rank_of[me.off + i]] = pts[me.off + i];
+}
 
 // ------------------------------------------------------------------ the union-find over grid positions
 // Invariant: parent[x] <= x, and parent[x] is x (x is a root) or an ancestor of x in the forest -- at every moment and
@@ -84,19 +245,28 @@ __global__ void __launch_bounds__(kBlock) k_cluster_init(unsigned *__restrict__ 
 
 // One lane per finite point, grid order.  Each edge once: the hit at the smaller position is joined by the lane at the
 // larger one (the lane itself, d2 = 0 at its own position, is no hit).  No cell-level shortcut: every pair is tested.
+// A batch: a workgroup (one wave) belongs to one scan, found from the table of first workgroups, so the scan's
+// lattice is the same for every lane (scalar registers) and its runs hold the scan's own points only; the positions
+// it joins are the batch's.
 __global__ void __launch_bounds__(kLinkBlock)
-    k_cluster_link(GridDev g, unsigned n, float r2, float r_cells, unsigned *parent) {
+    k_cluster_link(GridDev g, const ClScan *__restrict__ tab, unsigned S, unsigned n, float r2, float rf, unsigned *parent) {
     __shared__ uint2 s_runs[kKnnRows * kLinkBlock];
-    const unsigned i = blockIdx.x * kLinkBlock + threadIdx.x;
+    unsigned i = blockIdx.x * kLinkBlock + threadIdx.x;
+    if (tab) {
+        const unsigned k = cl_find(tab, S, blockIdx.x, [](const ClScan &s) { return s.lblk0; });
+        g = tab[k].g;
+        i = tab[k].g0 + (blockIdx.x - tab[k].lblk0) * kLinkBlock + threadIdx.x;
+        n = tab[k].g0 + tab[k].nf;
+    }
     if (i >= n) return;
     const float4 q = g.pts[i];
-    radius_walk<false>(g, q, r_cells, s_runs, threadIdx.x, kLinkBlock, [&](unsigned j, const float4 &t) {
+    radius_walk<false>(g, q, rf * g.inv_h, s_runs, threadIdx.x, kLinkBlock, [&](unsigned j, const float4 &t) {
         if (j < i && g_d2(q.x, q.y, q.z, t) < r2) uf_union(parent, i, j);
         return false;
     });
 }
 
-// (behind the link launch: the forest is final, a find only shortens paths)
+// (behind the link launch: the forest is final, a find only shortens paths)  c: the point's batch position
 __global__ void __launch_bounds__(kBlock)
     k_cluster_flatten(const float4 *__restrict__ gpts, unsigned n, unsigned *parent, unsigned *__restrict__ root_of,
                       unsigned *min_idx, unsigned *size) {
@@ -109,15 +279,34 @@ __global__ void __launch_bounds__(kBlock)
     atomicAdd(&size[r], 1u);
 }
 
-// res: [0] components, [1] kept clusters (k_cluster_keys), [2] points in kept clusters, [3] the largest kept cluster
+// res, four per scan: [0] components, [1] kept clusters (k_cluster_keys), [2] points in kept clusters, [3] the largest
+// kept cluster.  A wave whose 64 grid positions are of one scan adds its sums once; a wave across a scan boundary adds
+// root by root.
 __global__ void __launch_bounds__(kBlock)
     k_cluster_roots(const unsigned *__restrict__ size, unsigned n, unsigned lo, unsigned hi, unsigned *__restrict__ keep,
-                    unsigned *res) {
+                    unsigned *res, const ClScan *__restrict__ tab, unsigned S) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     const unsigned s = i < n ? size[i] : 0u;
     const bool kept = s >= lo && s <= hi && s > 0u;
     if (i < n) keep[i] = kept ? 1u : 0u;
     unsigned roots = s > 0u ? 1u : 0u, pts = kept ? s : 0u, big = pts;
+    if (tab) {
+        const unsigned w0 = i & ~63u;
+        if (w0 >= n) return;  // (the whole wave)
+        const unsigned k0 = cl_by_grid(tab, S, w0), k1 = cl_by_grid(tab, S, min(w0 + 63u, n - 1u));
+        if (k0 != k1) {
+            if (roots) {
+                unsigned *r = res + 4u * cl_by_grid(tab, S, i);
+                atomicAdd(&r[0], 1u);
+                if (pts) {
+                    atomicAdd(&r[2], pts);
+                    atomicMax(&r[3], big);
+                }
+            }
+            return;
+        }
+        res += 4u * k0;
+    }
     for (int off = 32; off > 0; off >>= 1) {
         roots += __shfl_down(roots, off);
         pts += __shfl_down(pts, off);
@@ -130,42 +319,60 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
-// pos = the exclusive scan of keep (n + 1 entries): the kept roots' sort keys and numbers, compacted
+// pos = the exclusive scan of keep (n + 1 entries): the kept roots' sort keys and numbers, compacted.  The key, most
+// significant first: the scan, (2^b - 1) - size, the smallest member's index in its scan -- fields of b bits (b = 32
+// and no scan field for the single call).  The grid positions are scan-major, so scan k's kept roots are pos's
+// increase over its positions.
 __global__ void __launch_bounds__(kBlock)
     k_cluster_keys(const unsigned *__restrict__ keep, const unsigned *__restrict__ pos, const unsigned *__restrict__ size,
                    const unsigned *__restrict__ min_idx, unsigned n, unsigned long long *__restrict__ keys,
-                   unsigned *__restrict__ vals, unsigned *__restrict__ res) {
+                   unsigned *__restrict__ vals, unsigned *__restrict__ res, const ClScan *__restrict__ tab, unsigned S,
+                   unsigned b) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i == 0) res[1] = pos[n];
+    if (!tab) {
+        if (i == 0) res[1] = pos[n];
+    } else if (i < S) {
+        res[4u * i + 1u] = pos[tab[i].g0 + tab[i].nf] - pos[tab[i].g0];
+    }
     if (i >= n || !keep[i]) return;
-    keys[pos[i]] = ((unsigned long long) (0xFFFFFFFFu - size[i]) << 32) | min_idx[i];
+    unsigned long long key;
+    if (tab) {
+        const unsigned k = cl_by_grid(tab, S, i);
+        key = ((unsigned long long) k << (2u * b)) | ((unsigned long long) (((1u << b) - 1u) - size[i]) << b) |
+              (min_idx[i] - tab[k].off);
+    } else {
+        key = ((unsigned long long) (0xFFFFFFFFu - size[i]) << 32) | min_idx[i];
+    }
+    keys[pos[i]] = key;
     vals[pos[i]] = i;
 }
 
-// sorted[r] = the root of the cluster of rank r
+// sorted[r] = the root of the cluster of rank r (batch-wide); lrank_of: its rank inside its scan, the label
 __global__ void __launch_bounds__(kBlock)
     k_cluster_rank(const unsigned *__restrict__ sorted, const unsigned *__restrict__ size, unsigned m,
-                   unsigned *__restrict__ rank_of, unsigned *__restrict__ size_by_rank) {
+                   unsigned *__restrict__ rank_of, unsigned *__restrict__ size_by_rank, const ClScan *__restrict__ tab,
+                   unsigned S, const unsigned *__restrict__ pos, unsigned *__restrict__ lrank_of) {
     const unsigned r = blockIdx.x * kBlock + threadIdx.x;
     if (r >= m) return;
     const unsigned root = sorted[r];
     rank_of[root] = r;
     size_by_rank[r] = size[root];
+    if (tab) lrank_of[root] = r - pos[tab[cl_by_grid(tab, S, root)].g0];
 }
 
-// caller order: the label, and the pair (rank, index) of the member sort -- a point of no kept cluster gets key m and
-// falls behind them all.  root_of[i] = kNoIdx: a non-finite point.
+// caller order: the label, and the pair (rank, position) of the member sort -- a point of no kept cluster gets key m
+// and falls behind them all.  root_of[i] = kNoIdx: a non-finite point.
 __global__ void __launch_bounds__(kBlock)
     k_cluster_labels(const unsigned *__restrict__ root_of, const unsigned *__restrict__ keep, const unsigned *__restrict__ rank_of,
-                     unsigned n, unsigned m, int *__restrict__ labels, unsigned *__restrict__ keys, unsigned *__restrict__ vals) {
+                     const unsigned *__restrict__ lrank_of, unsigned n, unsigned m, int *__restrict__ labels,
+                     unsigned *__restrict__ keys, unsigned *__restrict__ vals) {
     const unsigned i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const unsigned root = root_of[i];
-    int lab = WM_CLUSTER_NONE;
-    if (root != kNoIdx) lab = keep[root] ? (int) rank_of[root] : WM_CLUSTER_REJECTED;
-    if (labels) labels[i] = lab;
+    const bool in = root != kNoIdx && keep[root];
+    if (labels) labels[i] = in ? (int) lrank_of[root] : root != kNoIdx ? WM_CLUSTER_REJECTED : WM_CLUSTER_NONE;
     if (keys) {
-        keys[i] = lab >= 0 ? (unsigned) lab : m;
+        keys[i] = in ? rank_of[root] : m;
         vals[i] = i;
     }
 }
@@ -177,24 +384,50 @@ __global__ void __launch_bounds__(kBlock)
     if (c < count) out[c] = min(off[c], cap);
 }
 
+// The sorted member list (batch positions) -> the index inside the member's scan and, for points_out, its x y z as the
+// packed cloud holds them (a member is finite, and a finite point is packed bit for bit) in records of out_stride
+// bytes, the bytes behind z zero.
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_emit(const unsigned *__restrict__ sorted, unsigned count, const ClScan *__restrict__ tab, unsigned S,
+                   const float4 *__restrict__ pts, int *__restrict__ idx_out, unsigned char *__restrict__ pout,
+                   size_t out_stride) {
+    const unsigned j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= count) return;
+    const unsigned p = sorted[j];
+    if (idx_out) idx_out[j] = (int) (tab ? p - tab[cl_by_point(tab, S, p)].off : p);
+    if (pout) {
+        const float4 v = pts[p];
+        unsigned *o = reinterpret_cast<unsigned *>(pout + (size_t) j * out_stride);
+        o[0] = __float_as_uint(v.x);
+        o[1] = __float_as_uint(v.y);
+        o[2] = __float_as_uint(v.z);
+        for (size_t w = 3; w < out_stride / 4; ++w) o[w] = 0u;
+    }
+}
+
 }  // namespace
 
 // The context's workspace of the cluster extraction: its own buffers, shared with nothing else on the context.
 struct ClusterWs {
-    DevBuf pts, parent, root_of, min_idx, size, keep, pos, rank_of, size_by_rank, off, labels, offsets, res;
+    DevBuf pts, parent, root_of, min_idx, size, keep, pos, rank_of, lrank_of, size_by_rank, off, labels, offsets, res;
     DevBuf keys_a, keys_b, vals_a, vals_b, sort_tmp;  // the two sorts' ping-pong pairs
+    DevBuf idx, pout;                                 // host outputs on their way
+    DevBuf bb, cell_of, counts;                       // a batch's boxes and occupancies, and its counting sort
     GridLevel grid;
-    unsigned *h_res = nullptr;  // pinned: the four counters
+    PairStage stage;   // a batch's scan table and host clouds up (wm_stage.hpp)
+    PinnedBuf h_res;   // the counters, four per scan; a batch's boxes before them
 };
 
 void cluster_release(wm_ctx *ctx) {
     ClusterWs *w = static_cast<ClusterWs *>(ctx->cluster);
     if (!w) return;
     DevBuf *bufs[] = {&w->pts, &w->parent, &w->root_of, &w->min_idx, &w->size, &w->keep, &w->pos, &w->rank_of,
-                      &w->size_by_rank, &w->off, &w->labels, &w->offsets, &w->res, &w->keys_a, &w->keys_b, &w->vals_a,
-                      &w->vals_b, &w->sort_tmp, &w->grid.pts, &w->grid.cell_start};
+                      &w->lrank_of, &w->size_by_rank, &w->off, &w->labels, &w->offsets, &w->res, &w->keys_a, &w->keys_b,
+                      &w->vals_a, &w->vals_b, &w->sort_tmp, &w->idx, &w->pout, &w->bb, &w->cell_of, &w->counts,
+                      &w->grid.pts, &w->grid.cell_start};
     for (DevBuf *b : bufs) b->release();
-    if (w->h_res) (void) hipHostFree(w->h_res);
+    w->stage.release();
+    w->h_res.release();
     delete w;
     ctx->cluster = nullptr;
 }
@@ -213,6 +446,293 @@ int cluster_sort(wm_ctx *ctx, ClusterWs &w, K *k_in, K *k_out, unsigned *v_in, u
 }
 
 unsigned blocks_of(size_t n) { return (unsigned) ((n + kBlock - 1) / kBlock); }
+
+unsigned bits_of(unsigned long long v) {  // the bits that hold 0 ... v
+    unsigned b = 0;
+    while (b < 64 && (v >> b) != 0ull) ++b;
+    return b;
+}
+
+bool cl_args_ok(const wm_cluster_params *p, size_t stride, int mem, int out_mem) {
+    return p && stride >= 12 && !(stride & 3) && (mem == WM_MEM_HOST || mem == WM_MEM_DEVICE) &&
+           (out_mem == WM_MEM_HOST || out_mem == WM_MEM_DEVICE) && std::isfinite(p->tolerance) && p->tolerance > 0 &&
+           p->min_cluster_size >= 0 && p->max_cluster_size >= 0;
+}
+
+// What the front of a call (one scan or a batch) hands to the kernels behind the grid, and where the results go.
+struct ClCall {
+    const ClScan *tab = nullptr;  // nullptr: one scan, its grid in `g`
+    unsigned S = 1;
+    GridDev g{};
+    size_t n = 0, nf = 0;  // the call's points (batch positions) and the finite ones (grid positions)
+    unsigned link_blocks = 0, field_bits = 32;
+    const wm_cluster_params *p = nullptr;
+    bool host_out = true, timed = false;
+    int32_t *labels_out = nullptr, *indices_out = nullptr;
+    size_t cap = 0;
+    void *points_out = nullptr;
+    size_t out_stride = 0;
+    uint32_t *offsets_out = nullptr;
+    size_t cap_clusters = 0;
+    size_t m = 0, kept = 0;  // results: the kept clusters and their points; the counters are in w.h_res
+    float ms = 0.f;
+};
+
+// The device places of the outputs: the caller's own in device memory, else the workspace's.
+int cl_labels_place(wm_ctx *ctx, ClusterWs &w, const ClCall &c, int **d_labels) {
+    *d_labels = nullptr;
+    if (!c.labels_out) return WM_OK;
+    if (c.host_out) WM_HIP(ctx, w.labels.reserve(c.n * 4));
+    *d_labels = c.host_out ? w.labels.as<int>() : c.labels_out;
+    return WM_OK;
+}
+
+// A call without a finite point: every label NONE (-1: all bits set), no cluster.
+int cl_nothing_finite(wm_ctx *ctx, ClusterWs &w, const ClCall &c) {
+    hipStream_t st = ctx->stream;
+    int *d_labels = nullptr;
+    WM_TRY(cl_labels_place(ctx, w, c, &d_labels));
+    if (c.labels_out) WM_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, c.n * 4, st));
+    if (c.offsets_out && !c.host_out) WM_HIP(ctx, hipMemsetAsync(c.offsets_out, 0, 4, st));
+    WM_HIP(ctx, hipStreamSynchronize(st));
+    if (c.host_out) {
+        if (c.labels_out) WM_HIP(ctx, hipMemcpy(c.labels_out, d_labels, c.n * 4, hipMemcpyDeviceToHost));
+        if (c.offsets_out) c.offsets_out[0] = 0;
+    }
+    return WM_OK;
+}
+
+// Behind the grid: link, flatten, the size rule, the two sorts, the outputs.  One fetch (the counters of all scans) and
+// the wait at the end.  The single call: 4 memsets, 13 launches and the two sorts; a batch: one launch more
+// (k_cluster_emit) -- whatever the number of scans.
+int cl_back(wm_ctx *ctx, ClusterWs &w, ClCall &c) {
+    hipStream_t st = ctx->stream;
+    const size_t n = c.n, n_finite = c.nf;
+    const unsigned nf = (unsigned) n_finite, fblocks = blocks_of(n_finite), S = c.S;
+    const ClScan *tab = c.tab;
+    const float r2 = (float) (c.p->tolerance * c.p->tolerance);
+    const float rf = sqrtf(r2) * 1.0001f;  // (a point with float d2 < r2 lies within this of the query)
+    const GridDev &g = c.g;                // (a batch: only its pts, the shared array, is read from here)
+
+    int *d_labels = nullptr;
+    WM_TRY(cl_labels_place(ctx, w, c, &d_labels));
+    WM_HIP(ctx, w.root_of.reserve(n * 4));
+    WM_HIP(ctx, w.res.reserve((size_t) S * 4 * sizeof(unsigned)));
+    WM_HIP(ctx, w.h_res.reserve((size_t) S * 4 * sizeof(unsigned)));
+    WM_HIP(ctx, w.parent.reserve(n_finite * 4));
+    WM_HIP(ctx, w.min_idx.reserve(n_finite * 4));
+    WM_HIP(ctx, w.size.reserve(n_finite * 4));
+    WM_HIP(ctx, w.keep.reserve(n_finite * 4));
+    WM_HIP(ctx, w.pos.reserve((n_finite + 1) * 4));
+    WM_HIP(ctx, w.rank_of.reserve(n_finite * 4));
+    if (tab) WM_HIP(ctx, w.lrank_of.reserve(n_finite * 4));
+    WM_HIP(ctx, w.size_by_rank.reserve(n_finite * 4));
+    WM_HIP(ctx, w.off.reserve((n_finite + 1) * 4));
+    WM_HIP(ctx, w.keys_a.reserve(n * 8));
+    WM_HIP(ctx, w.keys_b.reserve(n * 8));
+    WM_HIP(ctx, w.vals_a.reserve(n * 4));
+    WM_HIP(ctx, w.vals_b.reserve(n * 4));
+    unsigned *parent = w.parent.as<unsigned>(), *root_of = w.root_of.as<unsigned>(), *min_idx = w.min_idx.as<unsigned>();
+    unsigned *size = w.size.as<unsigned>(), *keep = w.keep.as<unsigned>(), *pos = w.pos.as<unsigned>();
+    unsigned *res = w.res.as<unsigned>(), *rank_of = w.rank_of.as<unsigned>();
+    unsigned *lrank_of = tab ? w.lrank_of.as<unsigned>() : rank_of;
+    unsigned *h_res = w.h_res.as<unsigned>();
+
+    WM_HIP(ctx, hipMemsetAsync(root_of, 0xFF, n * 4, st));         // kNoIdx
+    WM_HIP(ctx, hipMemsetAsync(min_idx, 0xFF, n_finite * 4, st));
+    WM_HIP(ctx, hipMemsetAsync(size, 0, n_finite * 4, st));
+    WM_HIP(ctx, hipMemsetAsync(res, 0, (size_t) S * 4 * sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_cluster_init, dim3(fblocks), dim3(kBlock), 0, st, parent, nf);
+    hipLaunchKernelGGL(k_cluster_link, dim3(c.link_blocks), dim3(kLinkBlock), 0, st, g, tab, S, nf, r2, rf, parent);
+    hipLaunchKernelGGL(k_cluster_flatten, dim3(fblocks), dim3(kBlock), 0, st, g.pts, nf, parent, root_of, min_idx, size);
+    const unsigned lo = (unsigned) std::max(c.p->min_cluster_size, 1), hi = (unsigned) c.p->max_cluster_size;
+    hipLaunchKernelGGL(k_cluster_roots, dim3(fblocks), dim3(kBlock), 0, st, (const unsigned *) size, nf, lo, hi, keep, res,
+                       tab, S);
+    WM_HIP(ctx, hipGetLastError());
+    WM_TRY(exclusive_scan(ctx, keep, n_finite, pos));
+    hipLaunchKernelGGL(k_cluster_keys, dim3(blocks_of(std::max(n_finite, tab ? (size_t) S : (size_t) 0))), dim3(kBlock), 0, st,
+                       (const unsigned *) keep, (const unsigned *) pos, (const unsigned *) size, (const unsigned *) min_idx, nf,
+                       w.keys_a.as<unsigned long long>(), w.vals_a.as<unsigned>(), res, tab, S, c.field_bits);
+    WM_HIP(ctx, hipGetLastError());
+    WM_TRY(fast_fetch(ctx, h_res, res, (size_t) S * 4 * sizeof(unsigned)));
+    size_t m = 0, kept = 0;
+    for (unsigned k = 0; k < S; ++k) {
+        m += h_res[4 * k + 1];
+        kept += h_res[4 * k + 2];
+    }
+
+    const unsigned *sorted_pts = nullptr;
+    if (m > 0) {
+        const unsigned key_bits = tab ? bits_of(S - 1u) + 2u * c.field_bits : 64u;
+        WM_TRY(cluster_sort(ctx, w, w.keys_a.as<unsigned long long>(), w.keys_b.as<unsigned long long>(),
+                            w.vals_a.as<unsigned>(), w.vals_b.as<unsigned>(), m, std::max(key_bits, 1u)));
+        hipLaunchKernelGGL(k_cluster_rank, dim3(blocks_of(m)), dim3(kBlock), 0, st, (const unsigned *) w.vals_b.as<unsigned>(),
+                           (const unsigned *) size, (unsigned) m, rank_of, w.size_by_rank.as<unsigned>(), tab, S,
+                           (const unsigned *) pos, lrank_of);
+        WM_HIP(ctx, hipGetLastError());
+        WM_TRY(exclusive_scan(ctx, w.size_by_rank.as<unsigned>(), m, w.off.as<unsigned>()));
+    } else {
+        WM_HIP(ctx, hipMemsetAsync(w.off.p, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_cluster_labels, dim3(blocks_of(n)), dim3(kBlock), 0, st, (const unsigned *) root_of, (const unsigned *) keep,
+                       (const unsigned *) rank_of, (const unsigned *) lrank_of, (unsigned) n, (unsigned) m, d_labels,
+                       m > 0 ? w.keys_a.as<unsigned>() : (unsigned *) nullptr, w.vals_a.as<unsigned>());
+    WM_HIP(ctx, hipGetLastError());
+    if (m > 0) {
+        unsigned bits = 0;
+        while (((size_t) 1 << bits) <= m) ++bits;  // the keys are 0 ... m
+        WM_TRY(cluster_sort(ctx, w, w.keys_a.as<unsigned>(), w.keys_b.as<unsigned>(), w.vals_a.as<unsigned>(),
+                            w.vals_b.as<unsigned>(), n, bits));
+        sorted_pts = w.vals_b.as<unsigned>();
+    }
+    const size_t n_idx = std::min(kept, c.cap), n_off = std::min(m, c.cap_clusters) + 1;
+    unsigned *d_offsets = nullptr;
+    if (c.offsets_out) {
+        d_offsets = c.offsets_out;
+        if (c.host_out) {
+            WM_HIP(ctx, w.offsets.reserve(n_off * 4));
+            d_offsets = w.offsets.as<unsigned>();
+        }
+        hipLaunchKernelGGL(k_cluster_offsets, dim3(blocks_of(n_off)), dim3(kBlock), 0, st, (const unsigned *) w.off.as<unsigned>(),
+                           (unsigned) n_off, (unsigned) std::min(c.cap, (size_t) 0xFFFFFFFFu), d_offsets);
+        WM_HIP(ctx, hipGetLastError());
+    }
+    // the members: the sorted list itself for one scan without points_out, else through k_cluster_emit
+    const bool emit = n_idx && (tab || c.points_out);
+    const int *d_idx = reinterpret_cast<const int *>(sorted_pts);
+    unsigned char *d_pout = static_cast<unsigned char *>(c.points_out);
+    if (emit) {
+        int *idx = c.indices_out;
+        if (c.host_out) {
+            WM_HIP(ctx, w.idx.reserve(n_idx * 4));
+            idx = w.idx.as<int>();
+            if (c.points_out) {
+                WM_HIP(ctx, w.pout.reserve(n_idx * c.out_stride));
+                d_pout = w.pout.as<unsigned char>();
+            }
+        }
+        hipLaunchKernelGGL(k_cluster_emit, dim3(blocks_of(n_idx)), dim3(kBlock), 0, st, sorted_pts, (unsigned) n_idx, tab, S,
+                           (const float4 *) w.pts.as<float4>(), idx, d_pout, c.out_stride);
+        WM_HIP(ctx, hipGetLastError());
+        d_idx = idx;
+    } else if (!c.host_out && n_idx) {
+        WM_HIP(ctx, hipMemcpyAsync(c.indices_out, sorted_pts, n_idx * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (c.timed) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    WM_HIP(ctx, hipStreamSynchronize(st));
+    if (c.timed) (void) hipEventElapsedTime(&c.ms, ctx->ev_a, ctx->ev_b);
+    c.m = m;
+    c.kept = kept;
+    if (c.host_out) {
+        if (n_idx) WM_HIP(ctx, hipMemcpy(c.indices_out, d_idx, n_idx * 4, hipMemcpyDeviceToHost));
+        if (n_idx && c.points_out) WM_HIP(ctx, hipMemcpy(c.points_out, d_pout, n_idx * c.out_stride, hipMemcpyDeviceToHost));
+        if (c.offsets_out) WM_HIP(ctx, hipMemcpy(c.offsets_out, d_offsets, n_off * 4, hipMemcpyDeviceToHost));
+        if (c.labels_out) WM_HIP(ctx, hipMemcpy(c.labels_out, d_labels, n * 4, hipMemcpyDeviceToHost));
+    }
+    return kept > c.cap || m > c.cap_clusters ? WM_ERR_ARG : WM_OK;
+}
+
+void cl_stats_out(const unsigned *h, size_t n_finite, float ms, wm_cluster_stats *s) {
+    s->n_finite = n_finite;
+    s->n_components = h[0];
+    s->n_clusters = h[1];
+    s->n_clustered = h[2];
+    s->largest = h[3];
+    s->kernel_ms = ms;
+}
+
+// One scan, handed to the kernels by value: no table, no staging.  This is wm_cluster_extract, and
+// wm_cluster_extract_batch for a batch of one (arguments checked by the callers; the outputs zeroed).
+int cl_one(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const wm_cluster_params *p, int32_t *labels_out,
+           int32_t *indices_out, size_t cap, void *points_out, size_t out_stride, uint32_t *offsets_out, size_t cap_clusters,
+           int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats, float *kernel_ms) {
+    ClCall c;
+    c.host_out = out_mem == WM_MEM_HOST;
+    if (n == 0) {  // (no device is touched: offsets_out[0] can only be written where the host can write it)
+        if (offsets_out && c.host_out) offsets_out[0] = 0;
+        return WM_OK;
+    }
+    WM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->cluster) ctx->cluster = new ClusterWs();
+    ClusterWs &w = *static_cast<ClusterWs *>(ctx->cluster);
+    hipStream_t st = ctx->stream;
+    c.n = n;
+    c.p = p;
+    c.timed = stats || kernel_ms;
+    c.labels_out = labels_out;
+    c.indices_out = indices_out;
+    c.cap = cap;
+    c.points_out = points_out;
+    c.out_stride = points_out ? out_stride : 0;
+    c.offsets_out = offsets_out;
+    c.cap_clusters = cap_clusters;
+
+    WM_HIP(ctx, w.pts.reserve(n * sizeof(float4)));
+    if (c.timed) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+    WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.pts.as<float4>()));
+    Bbox bb;
+    size_t n_finite = 0;
+    WM_TRY(compute_bbox(ctx, w.pts.as<float4>(), n, &bb, &n_finite));
+    if (stats) stats->n_finite = n_finite;
+    if (n_finite == 0) return cl_nothing_finite(ctx, w, c);
+    WM_TRY(build_call_grid(ctx, w.pts.as<float4>(), n, n_finite, bb,
+                           fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div, &w.grid));
+    c.g = w.grid.d;
+    c.nf = n_finite;
+    c.link_blocks = (unsigned) ((n_finite + kLinkBlock - 1) / kLinkBlock);
+    const int rc = cl_back(ctx, w, c);
+    if (rc != WM_OK && rc != WM_ERR_ARG) return rc;
+    *n_out = c.kept;
+    *n_clusters = c.m;
+    if (stats) cl_stats_out(w.h_res.as<unsigned>(), n_finite, c.ms, stats);
+    if (kernel_ms) *kernel_ms = c.ms;
+    return rc;
+}
+
+// ------------------------------------------------------------------ a batch's lattices (host)
+uint64_t cl_cells_of(const Bbox &bb, float h) {  // (wm_grid.hip: build_grid_level's lattice)
+    uint64_t c = 1;
+    for (int d = 0; d < 3; ++d) c *= (uint64_t) floor(((double) bb.hi[d] - bb.lo[d]) / h) + 1;
+    return c;
+}
+
+// build_call_grid's automatic cell of a scan (occ == 0) or its second choice from the measured occupancy, under the
+// scan's share of the batch's cells
+float cl_cell_size(const Bbox &bb, size_t n_finite, float floor_h, uint64_t cell_cap, float h_prev, double occ) {
+    float h;
+    if (occ > 0) {
+        h = fmaxf((float) (h_prev * sqrt(3.0 / occ)), floor_h);
+    } else {
+        double vol = 1;
+        for (int d = 0; d < 3; ++d) vol *= fmax((double) bb.hi[d] - bb.lo[d], 1e-3);
+        h = fmaxf((float) fmax(cbrt(vol / (double) n_finite) * 1.5, 1e-4), floor_h);
+    }
+    while (cl_cells_of(bb, h) > cell_cap) h *= 1.26f;
+    return h;
+}
+
+void cl_lattice(const Bbox &bb, float h, GridDev *g) {  // (wm_grid.hip: build_grid_level)
+    g->nx = (int) floor((bb.hi[0] - bb.lo[0]) / h) + 1;
+    g->ny = (int) floor((bb.hi[1] - bb.lo[1]) / h) + 1;
+    g->nz = (int) floor((bb.hi[2] - bb.lo[2]) / h) + 1;
+    const float extent = fmaxf(fmaxf(bb.hi[0] - bb.lo[0], bb.hi[1] - bb.lo[1]), bb.hi[2] - bb.lo[2]);
+    float amax = 0;
+    for (int d = 0; d < 3; ++d) amax = fmaxf(amax, fmaxf(fabsf(bb.lo[d]), fabsf(bb.hi[d])));
+    const float ulp = fmaxf(amax, extent) * 1.2e-7f;
+    g->ox = bb.lo[0];
+    g->oy = bb.lo[1];
+    g->oz = bb.lo[2];
+    g->h = h;
+    g->inv_h = 1.0f / h;
+    g->slack = fmaxf(1e-3f, 8.0f * ulp / h);
+}
+
+float cl_from_orderable(unsigned u) {
+    const unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+    float f;
+    memcpy(&f, &b, 4);
+    return f;
+}
 
 }  // namespace
 
@@ -233,152 +753,187 @@ void wm_cluster_default_params(wm_cluster_params *p) {
 int wm_cluster_extract(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const wm_cluster_params *p,
                        int32_t *labels_out, int32_t *indices_out, size_t cap, uint32_t *offsets_out, size_t cap_clusters,
                        int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats) {
-    if (!ctx || !p || !n_out || !n_clusters || (n > 0 && !pts) || stride < 12 || (stride & 3) || n > 0x7FFFFFF0u ||
-        (cap > 0 && !indices_out) || (cap_clusters > 0 && !offsets_out) || (mem != WM_MEM_HOST && mem != WM_MEM_DEVICE) ||
-        (out_mem != WM_MEM_HOST && out_mem != WM_MEM_DEVICE) || !std::isfinite(p->tolerance) || !(p->tolerance > 0) ||
-        p->min_cluster_size < 0 || p->max_cluster_size < 0)
+    if (!ctx || !n_out || !n_clusters || (n > 0 && !pts) || n > 0x7FFFFFF0u || (cap > 0 && !indices_out) ||
+        (cap_clusters > 0 && !offsets_out) || !cl_args_ok(p, stride, mem, out_mem))
         return WM_ERR_ARG;
     *n_out = 0;
     *n_clusters = 0;
     if (stats) *stats = wm_cluster_stats{};
+    return cl_one(ctx, pts, n, stride, mem, p, labels_out, indices_out, cap, nullptr, 0, offsets_out, cap_clusters, out_mem,
+                  n_clusters, n_out, stats, nullptr);
+}
+
+int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_scans, size_t stride, int mem,
+                             const wm_cluster_params *p, int32_t *labels_out, int32_t *indices_out, size_t cap,
+                             void *points_out, size_t out_stride, uint32_t *offsets_out, size_t cap_clusters, int out_mem,
+                             size_t *cluster_first, size_t *n_out, wm_cluster_stats *stats, float *kernel_ms) {
+    if (!ctx || n_scans < 0 || (n_scans > 0 && !scans) || !cluster_first || !n_out || (cap > 0 && !indices_out) ||
+        (cap_clusters > 0 && !offsets_out) || (points_out && (out_stride < 12 || (out_stride & 3))) ||
+        !cl_args_ok(p, stride, mem, out_mem) || (unsigned long long) n_scans > WM_CLUSTER_BATCH_MAX_SCANS)
+        return WM_ERR_ARG;
+    const unsigned S = (unsigned) n_scans;
+    size_t total = 0, cloud_bytes = 0, blocks = 0, max_n = 0;
+    for (unsigned k = 0; k < S; ++k) {
+        if ((scans[k].n > 0 && !scans[k].pts) || scans[k].n > WM_CLUSTER_BATCH_MAX_POINTS) return WM_ERR_ARG;
+        total += scans[k].n;
+        if (total > WM_CLUSTER_BATCH_MAX_POINTS) return WM_ERR_ARG;
+        max_n = std::max(max_n, scans[k].n);
+        cloud_bytes += align_up256(scans[k].n * stride);
+        blocks += (scans[k].n + kBlock - 1) / kBlock;
+    }
+    // the sort key of a kept root: the scan, the size, the smallest index -- WM_CLUSTER_BATCH_KEY_BITS in all
+    const unsigned field_bits = std::max(bits_of(max_n), 1u);
+    if (S > 1 && bits_of(S - 1u) + 2u * field_bits > WM_CLUSTER_BATCH_KEY_BITS) return WM_ERR_ARG;
+    *n_out = 0;
+    for (unsigned k = 0; k <= S; ++k) cluster_first[k] = 0;
+    if (stats)
+        for (unsigned k = 0; k < S; ++k) stats[k] = wm_cluster_stats{};
+    if (kernel_ms) *kernel_ms = 0.f;
     const bool host_out = out_mem == WM_MEM_HOST;
-    if (n == 0) {  // (no device is touched: offsets_out[0] can only be written where the host can write it)
+    if (S == 0 || total == 0) {  // (no device is touched)
         if (offsets_out && host_out) offsets_out[0] = 0;
         return WM_OK;
+    }
+    if (S == 1) {  // a batch of one is the single call: nothing to stage, nothing to amortise
+        size_t m = 0;
+        const int rc = cl_one(ctx, scans[0].pts, scans[0].n, stride, mem, p, labels_out, indices_out, cap, points_out,
+                              out_stride, offsets_out, cap_clusters, out_mem, &m, n_out, stats, kernel_ms);
+        cluster_first[1] = m;
+        return rc;
     }
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->cluster) ctx->cluster = new ClusterWs();
     ClusterWs &w = *static_cast<ClusterWs *>(ctx->cluster);
-    if (!w.h_res) WM_HIP(ctx, hipHostMalloc((void **) &w.h_res, 4 * sizeof(unsigned), hipHostMallocDefault));
+    PairStage &stg = w.stage;
     hipStream_t st = ctx->stream;
-    const unsigned nblocks = blocks_of(n);
 
-    // the outputs' places: the caller's own in device memory, else the workspace's
-    WM_HIP(ctx, w.pts.reserve(n * sizeof(float4)));
-    WM_HIP(ctx, w.root_of.reserve(n * 4));
-    WM_HIP(ctx, w.res.reserve(4 * sizeof(unsigned)));
-    int *d_labels = nullptr;
-    if (labels_out) {
-        if (host_out) WM_HIP(ctx, w.labels.reserve(n * 4));
-        d_labels = host_out ? w.labels.as<int>() : labels_out;
-    }
-    unsigned *d_offsets = nullptr;
-    if (offsets_out) {
-        if (host_out) WM_HIP(ctx, w.offsets.reserve(4));
-        d_offsets = host_out ? w.offsets.as<unsigned>() : offsets_out;
-    }
+    ClCall c;
+    c.S = S;
+    c.n = total;
+    c.p = p;
+    c.field_bits = field_bits;
+    c.host_out = host_out;
+    c.timed = true;  // (PairStage::submit records ev_a)
+    c.labels_out = labels_out;
+    c.indices_out = indices_out;
+    c.cap = cap;
+    c.points_out = points_out;
+    c.out_stride = points_out ? out_stride : 0;
+    c.offsets_out = offsets_out;
+    c.cap_clusters = cap_clusters;
 
-    if (stats) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.pts.as<float4>()));
-    Bbox bb;
-    size_t n_finite = 0;
-    WM_TRY(compute_bbox(ctx, w.pts.as<float4>(), n, &bb, &n_finite));
-    if (stats) stats->n_finite = n_finite;
-    if (n_finite == 0) {  // every label NONE (-1: all bits set), no cluster
-        if (labels_out) WM_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, n * 4, st));
-        if (offsets_out) WM_HIP(ctx, hipMemsetAsync(d_offsets, 0, 4, st));
-        WM_HIP(ctx, hipStreamSynchronize(st));
-        if (host_out) {
-            if (labels_out) WM_HIP(ctx, hipMemcpy(labels_out, d_labels, n * 4, hipMemcpyDeviceToHost));
-            if (offsets_out) offsets_out[0] = 0;
+    // the table's first half and the clouds; pack, the boxes and the finite counts; their fetch
+    const size_t table_bytes = align_up256((size_t) S * sizeof(ClScan));
+    WM_TRY(stg.begin(ctx, table_bytes, cloud_bytes, 0, 0, mem));
+    ClScan *tab = stg.table<ClScan>();
+    unsigned off = 0, blk = 0;
+    for (unsigned k = 0; k < S; ++k) {
+        ClScan &t = tab[k];
+        t = ClScan{};
+        t.n = (unsigned) scans[k].n;
+        t.off = off;
+        t.blk0 = blk;
+        WM_TRY(stg.up.add(ctx, scans[k].pts, scans[k].n * stride, &t.raw));
+        off += t.n;
+        blk += (t.n + kBlock - 1) / kBlock;
+    }
+    c.tab = stg.d_table<ClScan>();
+    WM_HIP(ctx, w.pts.reserve(total * sizeof(float4)));
+    WM_HIP(ctx, w.bb.reserve((size_t) S * 8 * 4));
+    WM_HIP(ctx, w.h_res.reserve((size_t) S * 8 * 4));
+    unsigned *bb = w.bb.as<unsigned>(), *occ = bb + 7 * (size_t) S, *h_bb = w.h_res.as<unsigned>();
+    WM_TRY(stg.submit(ctx));
+    WM_HIP(ctx, hipMemsetAsync(bb, 0xFF, (size_t) S * 3 * 4, st));
+    WM_HIP(ctx, hipMemsetAsync(bb + 3 * (size_t) S, 0, (size_t) S * 5 * 4, st));
+    hipLaunchKernelGGL(k_cluster_pack, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S, stride, w.pts.as<float4>(), bb);
+    WM_HIP(ctx, hipGetLastError());
+    WM_TRY(fast_fetch(ctx, h_bb, bb, (size_t) S * 7 * 4));
+
+    // per scan: the finite count, the box, its grid positions and link workgroups
+    std::vector<Bbox> box(S);
+    std::vector<float> cell(S, 0.f);
+    std::vector<uint64_t> cell_cap(S, 0);
+    const float floor_h = fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div;
+    size_t nf_total = 0, lblk = 0;
+    for (unsigned k = 0; k < S; ++k) {
+        ClScan &t = tab[k];
+        t.nf = h_bb[6 * (size_t) S + k];
+        t.g0 = (unsigned) nf_total;
+        t.lblk0 = (unsigned) lblk;
+        nf_total += t.nf;
+        lblk += (t.nf + kLinkBlock - 1) / kLinkBlock;
+        if (stats) stats[k].n_finite = t.nf;
+        if (!t.nf) continue;
+        for (int d = 0; d < 3; ++d) {
+            box[k].lo[d] = cl_from_orderable(h_bb[3 * (size_t) k + d]);
+            box[k].hi[d] = cl_from_orderable(h_bb[3 * (size_t) S + 3 * (size_t) k + d]);
         }
-        return WM_OK;
+        // the single call's cap is 2^26 + 8 n cells; a batch shares ONE 2^26 among its scans
+        cell_cap[k] = std::min<uint64_t>(8ull * t.n + std::max<uint64_t>(((uint64_t) 1 << 26) / S, 4096), 0x7FFFFFFFull);
+        cell[k] = cl_cell_size(box[k], t.nf, floor_h, cell_cap[k], 0.f, 0.0);
     }
+    c.nf = nf_total;
+    c.link_blocks = (unsigned) lblk;
+    if (nf_total == 0) return cl_nothing_finite(ctx, w, c);
 
-    const float r2 = (float) (p->tolerance * p->tolerance);
-    const float rf = sqrtf(r2) * 1.0001f;  // (a point with float d2 < r2 lies within this of the query)
-    WM_TRY(build_call_grid(ctx, w.pts.as<float4>(), n, n_finite, bb,
-                           fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div, &w.grid));
-    const GridDev &g = w.grid.d;
-    const unsigned nf = (unsigned) n_finite, fblocks = blocks_of(n_finite);
-
-    WM_HIP(ctx, w.parent.reserve(n_finite * 4));
-    WM_HIP(ctx, w.min_idx.reserve(n_finite * 4));
-    WM_HIP(ctx, w.size.reserve(n_finite * 4));
-    WM_HIP(ctx, w.keep.reserve(n_finite * 4));
-    WM_HIP(ctx, w.pos.reserve((n_finite + 1) * 4));
-    WM_HIP(ctx, w.rank_of.reserve(n_finite * 4));
-    WM_HIP(ctx, w.size_by_rank.reserve(n_finite * 4));
-    WM_HIP(ctx, w.off.reserve((n_finite + 1) * 4));
-    WM_HIP(ctx, w.keys_a.reserve(n * 8));
-    WM_HIP(ctx, w.keys_b.reserve(n * 8));
-    WM_HIP(ctx, w.vals_a.reserve(n * 4));
-    WM_HIP(ctx, w.vals_b.reserve(n * 4));
-    unsigned *parent = w.parent.as<unsigned>(), *root_of = w.root_of.as<unsigned>(), *min_idx = w.min_idx.as<unsigned>();
-    unsigned *size = w.size.as<unsigned>(), *keep = w.keep.as<unsigned>(), *pos = w.pos.as<unsigned>();
-    unsigned *res = w.res.as<unsigned>();
-
-    WM_HIP(ctx, hipMemsetAsync(root_of, 0xFF, n * 4, st));         // kNoIdx
-    WM_HIP(ctx, hipMemsetAsync(min_idx, 0xFF, n_finite * 4, st));
-    WM_HIP(ctx, hipMemsetAsync(size, 0, n_finite * 4, st));
-    WM_HIP(ctx, hipMemsetAsync(res, 0, 4 * sizeof(unsigned), st));
-    hipLaunchKernelGGL(k_cluster_init, dim3(fblocks), dim3(kBlock), 0, st, parent, nf);
-    hipLaunchKernelGGL(k_cluster_link, dim3((unsigned) ((n_finite + kLinkBlock - 1) / kLinkBlock)), dim3(kLinkBlock), 0, st,
-                       g, nf, r2, rf * g.inv_h, parent);
-    hipLaunchKernelGGL(k_cluster_flatten, dim3(fblocks), dim3(kBlock), 0, st, g.pts, nf, parent, root_of, min_idx, size);
-    const unsigned lo = (unsigned) std::max(p->min_cluster_size, 1), hi = (unsigned) p->max_cluster_size;
-    hipLaunchKernelGGL(k_cluster_roots, dim3(fblocks), dim3(kBlock), 0, st, (const unsigned *) size, nf, lo, hi, keep, res);
-    WM_HIP(ctx, hipGetLastError());
-    WM_TRY(exclusive_scan(ctx, keep, n_finite, pos));
-    hipLaunchKernelGGL(k_cluster_keys, dim3(fblocks), dim3(kBlock), 0, st, (const unsigned *) keep, (const unsigned *) pos,
-                       (const unsigned *) size, (const unsigned *) min_idx, nf, w.keys_a.as<unsigned long long>(),
-                       w.vals_a.as<unsigned>(), res);
-    WM_HIP(ctx, hipGetLastError());
-    WM_TRY(fast_fetch(ctx, w.h_res, res, 4 * sizeof(unsigned)));
-    const size_t n_comp = w.h_res[0], m = w.h_res[1], kept = w.h_res[2], largest = w.h_res[3];
-
-    const unsigned *sorted_pts = nullptr;
-    if (m > 0) {
-        WM_TRY(cluster_sort(ctx, w, w.keys_a.as<unsigned long long>(), w.keys_b.as<unsigned long long>(),
-                            w.vals_a.as<unsigned>(), w.vals_b.as<unsigned>(), m, 64u));
-        hipLaunchKernelGGL(k_cluster_rank, dim3(blocks_of(m)), dim3(kBlock), 0, st, (const unsigned *) w.vals_b.as<unsigned>(),
-                           (const unsigned *) size, (unsigned) m, w.rank_of.as<unsigned>(), w.size_by_rank.as<unsigned>());
-        WM_HIP(ctx, hipGetLastError());
-        WM_TRY(exclusive_scan(ctx, w.size_by_rank.as<unsigned>(), m, w.off.as<unsigned>()));
-    } else {
-        WM_HIP(ctx, hipMemsetAsync(w.off.p, 0, 4, st));
-    }
-    hipLaunchKernelGGL(k_cluster_labels, dim3(nblocks), dim3(kBlock), 0, st, (const unsigned *) root_of, (const unsigned *) keep,
-                       (const unsigned *) w.rank_of.as<unsigned>(), (unsigned) n, (unsigned) m, d_labels,
-                       m > 0 ? w.keys_a.as<unsigned>() : (unsigned *) nullptr, w.vals_a.as<unsigned>());
-    WM_HIP(ctx, hipGetLastError());
-    if (m > 0) {
-        unsigned bits = 0;
-        while (((size_t) 1 << bits) <= m) ++bits;  // the keys are 0 ... m
-        WM_TRY(cluster_sort(ctx, w, w.keys_a.as<unsigned>(), w.keys_b.as<unsigned>(), w.vals_a.as<unsigned>(),
-                            w.vals_b.as<unsigned>(), n, bits));
-        sorted_pts = w.vals_b.as<unsigned>();
-    }
-    const size_t n_idx = std::min(kept, cap), n_off = std::min(m, cap_clusters) + 1;
-    if (offsets_out) {
-        if (host_out) {
-            WM_HIP(ctx, w.offsets.reserve(n_off * 4));
-            d_offsets = w.offsets.as<unsigned>();
+    // the lattices, cells numbered scan after scan: count, (the occupancies' fetch, at most one recount), scan, scatter
+    WM_HIP(ctx, w.grid.pts.reserve((total + 4) * sizeof(float4)));
+    WM_HIP(ctx, w.cell_of.reserve(2 * total * 4));
+    unsigned *cell_of = w.cell_of.as<unsigned>(), *rank_of = cell_of + total;
+    uint64_t ncells = 0;
+    for (int attempt = 0;; ++attempt) {
+        ncells = 0;
+        for (unsigned k = 0; k < S; ++k) {
+            ClScan &t = tab[k];
+            t.cell0 = ncells;
+            if (!t.nf) continue;
+            cl_lattice(box[k], cell[k], &t.g);
+            ncells += (uint64_t) t.g.nx * t.g.ny * t.g.nz;
         }
-        hipLaunchKernelGGL(k_cluster_offsets, dim3(blocks_of(n_off)), dim3(kBlock), 0, st, (const unsigned *) w.off.as<unsigned>(),
-                           (unsigned) n_off, (unsigned) std::min(cap, (size_t) 0xFFFFFFFFu), d_offsets);
+        // (the stream is idle here -- both fetches have been waited for -- so growing a buffer frees nothing in use)
+        WM_HIP(ctx, w.grid.cell_start.reserve((ncells + 1) * 4));
+        WM_HIP(ctx, w.counts.reserve(ncells * 4));
+        for (unsigned k = 0; k < S; ++k) {
+            tab[k].g.pts = w.grid.pts.as<float4>();
+            tab[k].g.cell_start = w.grid.cell_start.as<unsigned>() + tab[k].cell0;
+        }
+        WM_HIP(ctx, hipMemcpyAsync(stg.up.dev.p, stg.up.host.p, table_bytes, hipMemcpyHostToDevice, st));
+        WM_HIP(ctx, hipMemsetAsync(w.counts.p, 0, ncells * 4, st));
+        hipLaunchKernelGGL(k_cluster_count, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S,
+                           (const float4 *) w.pts.as<float4>(), cell_of, rank_of, w.counts.as<unsigned>(), occ);
         WM_HIP(ctx, hipGetLastError());
+        if (attempt) break;
+        WM_TRY(fast_fetch(ctx, h_bb, occ, (size_t) S * 4));
+        bool again = false;
+        for (unsigned k = 0; k < S; ++k) {
+            if (!tab[k].nf || !h_bb[k]) continue;
+            const double o = (double) tab[k].nf / h_bb[k];
+            if (o > 6.0 || o < 1.5) {
+                const float h2 = cl_cell_size(box[k], tab[k].nf, floor_h, cell_cap[k], cell[k], o);
+                again = again || h2 != cell[k];
+                cell[k] = h2;
+            }
+        }
+        if (!again) break;
     }
-    if (!host_out && n_idx)
-        WM_HIP(ctx, hipMemcpyAsync(indices_out, sorted_pts, n_idx * 4, hipMemcpyDeviceToDevice, st));
-    if (stats) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    WM_HIP(ctx, hipStreamSynchronize(st));
+    WM_TRY(exclusive_scan(ctx, w.counts.as<unsigned>(), ncells, w.grid.cell_start.as<unsigned>()));
+    hipLaunchKernelGGL(k_cluster_scatter, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S,
+                       (const float4 *) w.pts.as<float4>(), (const unsigned *) cell_of, (const unsigned *) rank_of,
+                       (const unsigned *) w.grid.cell_start.as<unsigned>(), w.grid.pts.as<float4>(), (size_t) ncells);
+    WM_HIP(ctx, hipGetLastError());
+    c.g = GridDev{};
+    c.g.pts = w.grid.pts.as<float4>();
 
-    *n_out = kept;
-    *n_clusters = m;
-    if (stats) {
-        stats->n_components = n_comp;
-        stats->n_clusters = m;
-        stats->n_clustered = kept;
-        stats->largest = largest;
-        (void) hipEventElapsedTime(&stats->kernel_ms, ctx->ev_a, ctx->ev_b);
+    const int rc = cl_back(ctx, w, c);
+    if (rc != WM_OK && rc != WM_ERR_ARG) return rc;
+    *n_out = c.kept;
+    const unsigned *h = w.h_res.as<unsigned>();
+    for (unsigned k = 0; k < S; ++k) {
+        cluster_first[k + 1] = cluster_first[k] + h[4 * k + 1];
+        if (stats) cl_stats_out(h + 4 * k, tab[k].nf, c.ms, &stats[k]);
     }
-    if (host_out) {
-        if (n_idx) WM_HIP(ctx, hipMemcpy(indices_out, sorted_pts, n_idx * 4, hipMemcpyDeviceToHost));
-        if (offsets_out) WM_HIP(ctx, hipMemcpy(offsets_out, d_offsets, n_off * 4, hipMemcpyDeviceToHost));
-        if (labels_out) WM_HIP(ctx, hipMemcpy(labels_out, d_labels, n * 4, hipMemcpyDeviceToHost));
-    }
-    return kept > cap || m > cap_clusters ? WM_ERR_ARG : WM_OK;
+    if (kernel_ms) *kernel_ms = c.ms;
+    return rc;
 }
 
 }  // extern "C"

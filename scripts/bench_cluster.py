@@ -10,7 +10,13 @@ beside it.  Prints one JSON line.
 --yardstick N        N rounds per cloud and tolerance of: wm_cluster_extract (k_cluster_link), then the radius outlier
                      filter with counts_out at radius = tolerance (k_outlier_radius<true>: the same walk over the same
                      grid rule without the unions).  Meant to run under `rocprofv3 --kernel-trace --stats`, whose
-                     per-kernel times are the comparison -- link / radius is what the unions cost; nothing else is timed."""
+                     per-kernel times are the comparison -- link / radius is what the unions cost; nothing else is timed.
+--batch S[,S...]     adds the key "batch": wm_cluster_extract_batch over S scans against the same S scans through
+                     wm_cluster_extract one after the other on the same context, the two alternating; ms PER SCAN, the
+                     median of --rounds rounds, one entry per repeat (--repeats).  Device input, tolerance 0.2 and
+                     0.5 m; the scans: the obstacle points wm_ground_segment_batch keeps from
+                     rings_sensor_frame(130 000, seed 42 + k), and the 3 000-point stress shapes of the tests in turn.
+                     --skip-plain leaves the single-call part out."""
 import argparse
 import json
 import os
@@ -37,8 +43,55 @@ def timed(ctx, cloud, calls, warmup, tolerance):
             "clusters": int(r["n_clusters"]), "largest": int(r["largest"])}
 
 
+def bench_batch(ctx, sizes, rounds, warmup, repeats, tolerances):
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ground_scenes as S
+    import knn_reference as KR
+    top = max(sizes)
+    rings = []
+    for k0 in range(0, top, 8):  # (eight scans per filter call: the ground workspace stays small)
+        scans = [torch.from_numpy(S.rings_sensor_frame(130_000, 42 + k)).to("cuda") for k in range(k0, min(k0 + 8, top))]
+        _, kept, offs = ctx.ground_segment_batch(scans, points=True)
+        rings += [kept[offs[j]:offs[j + 1]].clone() for j in range(len(scans))]
+    shapes = KR.shapes()
+    stress = [torch.from_numpy(np.ascontiguousarray(shapes[KR.NAMES[k % len(KR.NAMES)]])).to("cuda") for k in range(top)]
+    work = {"rings_130k_obstacles": rings, "stress_3000": stress}
+    out = {"metric": "ms per scan (median of rounds; one entry per repeat)", "rounds": rounds, "repeats": repeats}
+    for name, scans in work.items():
+        out[name] = {"points_per_scan": int(np.mean([len(s) for s in scans]))}
+    torch.cuda.synchronize()
+    for _ in range(repeats):  # the whole measurement, again
+        for name, scans in work.items():
+            for tol in tolerances:
+                for S_ in sizes:
+                    clouds = scans[:S_]
+                    for _ in range(max(warmup // S_, 3)):
+                        for c in clouds:
+                            ctx.cluster_extract(c, tolerance=tol)
+                        ctx.cluster_extract_batch(clouds, tolerance=tol)
+                    tl, tb = [], []
+                    for _ in range(rounds):
+                        t0 = time.perf_counter()
+                        for c in clouds:
+                            ctx.cluster_extract(c, tolerance=tol)
+                        t1 = time.perf_counter()
+                        ctx.cluster_extract_batch(clouds, tolerance=tol)
+                        t2 = time.perf_counter()
+                        tl.append((t1 - t0) * 1e3 / S_)
+                        tb.append((t2 - t1) * 1e3 / S_)
+                    cell = out[name].setdefault("tolerance_%g_S%d" % (tol, S_), {"loop_ms_per_scan": [], "batch_ms_per_scan": []})
+                    cell["loop_ms_per_scan"].append(round(float(np.median(tl)), 4))
+                    cell["batch_ms_per_scan"].append(round(float(np.median(tb)), 4))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default="", help="S[,S...]: also time wm_cluster_extract_batch against a loop of single calls")
+    ap.add_argument("--rounds", type=int, default=200, help="rounds of a --batch cell")
+    ap.add_argument("--repeats", type=int, default=5, help="repeats of the whole --batch measurement")
+    ap.add_argument("--skip-plain", action="store_true", help="with --batch: leave the single-call part out")
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--clouds", default="scene_1m,rings_2m_obstacles")
@@ -58,7 +111,8 @@ def main():
 
     make = {"scene_1m": lambda: torch.from_numpy(synth.scene(1_000_000, seed=42)).to("cuda"), "rings_2m_obstacles": obstacles}
     out = {"metric": "wm_cluster_extract ms per call, cloud in device memory (median of calls)", "calls": a.calls}
-    for name in [c for c in a.clouds.split(",") if c]:
+    sizes = [int(x) for x in a.batch.split(",") if x]
+    for name in [c for c in a.clouds.split(",") if c and not (sizes and a.skip_plain)]:
         cloud = make[name]()
         torch.cuda.synchronize()
         row = {"points": int(len(cloud))}
@@ -78,6 +132,8 @@ def main():
                 ctx.set_option("cluster_cell_div", 2.0)
         out[name] = row
         del cloud
+    if sizes:
+        out["batch"] = bench_batch(ctx, sizes, a.rounds, a.warmup, a.repeats, TOLERANCES)
     ctx.close()
     print(json.dumps(out))
 
