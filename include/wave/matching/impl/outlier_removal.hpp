@@ -42,6 +42,32 @@ void OutlierRemoval<PointT>::applyFilter(PointCloud &output) {
     pcl::copyPointCloud(in, out_indices, output);
 }
 
+template <typename PointT>
+void OutlierRemoval<PointT>::filterBatch(const std::vector<PointCloudConstPtr> &inputs, std::vector<PointCloud> &outputs) {
+    static_assert(sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) % 4 == 0,
+                  "OutlierRemoval: a point type whose first three floats are x, y, z");
+    const PointCloud none;
+    const size_t count = inputs.size();
+    std::vector<const void *> pts(count, nullptr);
+    std::vector<size_t> n(count, 0);
+    std::vector<unsigned char> null_cloud(count, 0);  // (not vector<bool>: the flags go over as an array)
+    for (size_t k = 0; k < count; ++k) {
+        if (!inputs[k]) {
+            null_cloud[k] = 1;
+            continue;
+        }
+        n[k] = inputs[k]->points.size();
+        if (n[k]) pts[k] = inputs[k]->points.data();
+    }
+    std::vector<std::vector<int>> kept;
+    if (!detail::outlierIndicesBatch(this->ctx, this->device, pts.data(), n.data(), null_cloud.data(), count,
+                                     sizeof(PointT), this->params, kept))
+        kept.assign(count, std::vector<int>());
+    std::vector<PointCloud> result(count);  // (formed aside: `outputs` may hold the inputs' clouds)
+    for (size_t k = 0; k < count; ++k) pcl::copyPointCloud(inputs[k] ? *inputs[k] : none, kept[k], result[k]);
+    outputs.swap(result);
+}
+
 }  // namespace wave
 
 // PCL_INSTANTIATE_OutlierRemoval(MyPoint) in one source file of a program precompiles the filter for MyPoint

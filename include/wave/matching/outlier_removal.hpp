@@ -13,6 +13,9 @@
 // with either setting of setNegative (PCL keeps it).  libwave_matching.so holds the pcl::PointXYZ instantiation;
 // any other point type whose first three floats are x, y, z works after
 // #include <wave/matching/impl/outlier_removal.hpp>.
+//
+// filterBatch() filters a queue of scans in ONE C-ABI call, wm_outlier_filter_batch: every output equals what filter()
+// gives for that scan alone, and the per-call cost (the packing, the grid, the fetches and the wait) is paid once.
 #ifndef WAVE_OUTLIERREMOVAL_HPP
 #define WAVE_OUTLIERREMOVAL_HPP
 
@@ -51,12 +54,19 @@ void outlierRelease(wm_ctx *&ctx);
 // the kept points' indices, ascending; false (after a LOG_ERROR) on bad parameters or a device error
 bool outlierIndices(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride,
                     const OutlierRemovalParams &params, std::vector<int> &out);
+// the same for `count` clouds in one wm_outlier_filter_batch call: out[k] = cloud k's kept indices.  A null cloud
+// (null_cloud[k]) is logged and gives an empty list, as a cloud that is not converged does; false (after a LOG_ERROR,
+// every list empty) on bad parameters or a device error
+bool outlierIndicesBatch(wm_ctx *&ctx, int device, const void *const *pts, const size_t *n, const unsigned char *null_cloud,
+                         size_t count, size_t stride, const OutlierRemovalParams &params,
+                         std::vector<std::vector<int>> &out);
 }  // namespace detail
 
 template <typename PointT>
 class OutlierRemoval : public pcl::Filter<PointT> {
  public:
     using PointCloud = typename pcl::Filter<PointT>::PointCloud;
+    using PointCloudConstPtr = typename pcl::Filter<PointT>::PointCloudConstPtr;
 
     explicit OutlierRemoval(const OutlierRemovalParams &config);  // no device is opened here
     OutlierRemoval(const OutlierRemoval &other);                  // the copy opens a context of its own
@@ -68,6 +78,11 @@ class OutlierRemoval : public pcl::Filter<PointT> {
 
     // filters input_ on the device (wm_outlier_filter) and copies the kept points to `output`, in input order
     void applyFilter(PointCloud &output) override;
+
+    // filter() for every cloud of `inputs` in one device call (wm_outlier_filter_batch): outputs[k] equals what
+    // setInputCloud(inputs[k]) + filter() gives.  A null cloud is logged and gives an empty output, as a cloud with
+    // fewer than mean_k + 1 finite points does; bad parameters or a device error log and give empty outputs.
+    void filterBatch(const std::vector<PointCloudConstPtr> &inputs, std::vector<PointCloud> &outputs);
 
  private:
     OutlierRemovalParams params;

@@ -800,6 +800,42 @@ int wm_outlier_filter(wm_ctx *ctx, const void *pts, size_t n, size_t stride_byte
                       int32_t *counts_out /* NULL ok, radius; -1 for a non-finite point */,
                       wm_outlier_stats *stats /* NULL ok */);
 
+/* A queue of scans in one device call: the same steps with a scan dimension, one `p`, one stride and one `mem` for
+ * the batch (as wm_ground_segment_batch and wm_cluster_extract_batch), in a number of launches and host waits that
+ * does not depend on n_scans.  For every scan k, status[k], the slice [offsets_out[k], offsets_out[k + 1]) of
+ * indices_out (indices local to the scan, ascending), its slices of labels_out, mean_dist_out and counts_out (the
+ * scans' n entries one after the other) and stats[k] (but kernel_ms, which is the batch's) EQUAL what
+ * wm_outlier_filter returns for that scan alone with the same `p` -- the bits of mean, stddev and threshold included,
+ * whatever the other scans of the batch are and whatever their order.  points_out (NULL: not wanted): per kept index
+ * the input point's x y z, bit for bit, in records of out_stride bytes (>= 12, a multiple of 4; the bytes behind z are
+ * zero) -- wm_ground_segment_batch's rules, and what wm_cluster_extract_batch(mem = WM_MEM_DEVICE) takes as it is.
+ * out_mem says where indices_out, points_out, labels_out, mean_dist_out and counts_out live; offsets_out (n_scans + 1
+ * entries), status and stats (n_scans entries) are host memory.
+ * The call returns WM_OK when the batch ran.  A statistical scan with 0 < n_finite < mean_k + 1 has status[k] =
+ * WM_NOT_CONVERGED, an empty slice of indices and stats[k] zero but n_finite; its slices of labels, distances and
+ * counts hold 0 / WM_OUTLIER_NONE and carry no meaning; its points are not searched.  Empty scans and scans without a
+ * finite point are WM_OK with empty slices (labels NONE, distance 0, count -1).  n_scans == 0, or no point in any
+ * scan: WM_OK with no device touched and every offset 0.  More kept points than `cap`: WM_ERR_ARG with the offsets the
+ * true ones (the first `cap` indices and points are written).  Argument errors, found before a device is touched:
+ * wm_outlier_filter's, a null scans / offsets_out / status, a scan with a null pts and n > 0, a bad out_stride with
+ * points_out, and a batch beyond the two limits below.  A batch of one scan is the single call.
+ * Each scan has a lattice of its own; where the single call allows a scan 2^26 + 8 n cells, a batch allows scan k
+ * 8 n_k + max(2^26 / n_scans, 4096): one 2^26 for the whole batch (wm_cluster_extract_batch's rule).  Coarser cells
+ * change no output.  kernel_ms (NULL ok): device time from the upload to the kept list.  The workspace is the one of
+ * wm_outlier_filter; the registration state and the ground and cluster workspaces are not touched. */
+typedef struct { const void *pts; size_t n; } wm_outlier_scan;
+#define WM_OUTLIER_BATCH_MAX_POINTS 0x7FFFFFF0ull /* the scans' points in all, at most */
+#define WM_OUTLIER_BATCH_MAX_SCANS 0x1000000ull   /* n_scans at most */
+int wm_outlier_filter_batch(wm_ctx *ctx, const wm_outlier_scan *scans, int n_scans, size_t stride_bytes, int mem,
+                            const wm_outlier_params *p,
+                            int32_t *indices_out, size_t cap,
+                            void *points_out /* NULL ok */, size_t out_stride,
+                            int out_mem, size_t *offsets_out /* host, n_scans + 1 entries */,
+                            uint8_t *labels_out /* NULL ok */, float *mean_dist_out /* NULL ok, statistical */,
+                            int32_t *counts_out /* NULL ok, radius */,
+                            int *status /* host, n_scans entries */, wm_outlier_stats *stats /* NULL ok: n_scans entries */,
+                            float *kernel_ms /* NULL ok */);
+
 /* ------------------------------------------------------------- Euclidean cluster extraction */
 /* pcl::EuclideanClusterExtraction on the device: the step between GroundSegmentation's obstacle points and a
  * registration.  [PCL-upstream: restated from PCL 1.8 segmentation/impl/extract_clusters.hpp; no PCL on the build

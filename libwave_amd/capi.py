@@ -134,6 +134,13 @@ WM_OUTLIER_NONE, WM_OUTLIER_INLIER, WM_OUTLIER_OUTLIER = 0, 1, 2
 WM_OUTLIER_MAX_MEAN_K = 31  # the k-NN search keeps lists of 32, the point itself among them
 
 
+class OutlierScan(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_size_t)]
+
+
+WM_OUTLIER_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of an outlier_filter_batch's scans in all
+WM_OUTLIER_BATCH_MAX_SCANS = 0x1000000
+
 
 class ClusterParams(C.Structure):
     _fields_ = [("tolerance", C.c_double), ("min_cluster_size", C.c_int), ("max_cluster_size", C.c_int)]
@@ -300,6 +307,10 @@ def lib():
         L.wm_outlier_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(OutlierParams),
                                         C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(OutlierStats)]
+        L.wm_outlier_filter_batch.argtypes = [C.c_void_p, C.POINTER(OutlierScan), C.c_int, C.c_size_t, C.c_int,
+                                              C.POINTER(OutlierParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int), C.POINTER(OutlierStats), C.POINTER(C.c_float)]
         L.wm_cluster_default_params.argtypes = [C.POINTER(ClusterParams)]
         L.wm_cluster_default_params.restype = None
         L.wm_cluster_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(ClusterParams),
@@ -638,6 +649,75 @@ class Context:
             out["labels"] = labels[:n]
             out["mean_dist" if stat else "counts"] = extra[:n] if extra is not None else None
         out.update({k: getattr(st, k) for k, _ in OutlierStats._fields_})
+        return out
+
+    def outlier_filter_batch(self, clouds, params=None, counts=True, points=False, out_mem=None, **kw):
+        """outlier_filter for a queue of scans in one device call (wm_outlier_filter_batch) -> one dict per scan with
+        the keys of outlier_filter, each EQUAL to outlier_filter's for that scan alone (rc is the scan's status, the
+        arrays None where it is not WM_OK; kernel_ms is the batch's).  `clouds`: float32 (n, 3|4) numpy arrays or HIP
+        torch tensors (separate allocations are fine), all of one kind; one `params` for the batch.  out_mem: where the
+        arrays are written, WM_MEM_HOST (numpy) or WM_MEM_DEVICE (torch tensors); by default where the clouds live.
+        points=True: every dict also has `points`, the scan's kept points (m, 3|4) float32 in the order of its
+        indices -- slices of ONE array that cluster_extract_batch takes as they are.  More kept points than the
+        call's capacity cannot happen here (the capacity is the batch's points)."""
+        n_scans = len(clouds)
+        if isinstance(params, OutlierParams):
+            params = {k: getattr(params, k) for k, _ in OutlierParams._fields_}
+        p = outlier_params(params, **kw)
+        stat = p.method == WM_OUTLIER_STATISTICAL
+        scans = (OutlierScan * max(n_scans, 1))()
+        alive, stride, mem, sizes = [], None, None, []
+        for k, cloud in enumerate(clouds):
+            ptr, n, sk, mk, a = _cloud_arg(cloud)
+            assert stride in (None, sk) and mem in (None, mk), "the scans of a batch share one layout and one memory"
+            stride, mem = sk, mk
+            alive.append(a)
+            scans[k].pts, scans[k].n = ptr, n
+            sizes.append(n)
+        stride, mem = stride or 12, WM_MEM_HOST if mem is None else mem
+        out_mem = mem if out_mem is None else out_mem
+        total = sum(sizes)
+        offs = (C.c_size_t * (n_scans + 1))()
+        status = (C.c_int * max(n_scans, 1))()
+        st = (OutlierStats * max(n_scans, 1))()
+        ms = C.c_float(0)
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = clouds[0].device if mem == WM_MEM_DEVICE and n_scans else "cuda:%d" % self.device
+            idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+            labels = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+            extra = (torch.zeros(max(total, 1), dtype=torch.float32, device=dev) if stat else
+                     torch.full((max(total, 1),), -1, dtype=torch.int32, device=dev) if counts else None)
+            kept = torch.zeros((max(total, 1), stride // 4), dtype=torch.float32, device=dev) if points else None
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            idx = np.empty(max(total, 1), np.int32)
+            labels = np.zeros(max(total, 1), np.uint8)
+            extra = np.zeros(max(total, 1), np.float32) if stat else np.full(max(total, 1), -1, np.int32) if counts else None
+            kept = np.zeros((max(total, 1), stride // 4), np.float32) if points else None
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        self._check(lib().wm_outlier_filter_batch(self._h, scans, n_scans, stride, mem, C.byref(p), addr(idx), total,
+                                                  addr(kept), stride if points else 0, out_mem, offs, addr(labels),
+                                                  addr(extra) if stat else None, None if stat else addr(extra), status, st,
+                                                  C.byref(ms)), "wm_outlier_filter_batch")
+        out, at = [], 0
+        for k in range(n_scans):
+            a, b = int(offs[k]), int(offs[k + 1])
+            d = dict(rc=status[k], indices=idx[a:b], labels=None, mean_dist=None, counts=None)
+            if status[k] == WM_OK:
+                d["labels"] = labels[at:at + sizes[k]]
+                d["mean_dist" if stat else "counts"] = extra[at:at + sizes[k]] if extra is not None else None
+            d.update({f: getattr(st[k], f) for f, _ in OutlierStats._fields_})
+            d["kernel_ms"] = ms.value
+            if points:
+                d["points"] = kept[a:b]
+            out.append(d)
+            at += sizes[k]
         return out
 
     def cluster_extract(self, cloud, params=None, labels=True, out_mem=None, **kw):

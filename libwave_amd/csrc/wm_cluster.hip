@@ -24,18 +24,18 @@
 // clusters comes from (size, smallest caller index) alone.
 //
 // A batch (ClScan: a scan's row of the device table; tab == nullptr is the single call, its scan handed over by
-// value): the scans' points stand one after the other ("batch positions", scan-major), each scan has a lattice of its
-// own whose cells are numbered scan after scan, so one count, one exclusive scan and one scatter give ONE cell-sorted
-// array, scan-major again ("grid positions").  A scan's GridDev points at its own slice of cell_start and at the
-// shared array, so a walk never meets a point of another scan, and the union-find, the counters, the two sorts and
-// the outputs run over the whole batch at once: the sort key of a kept root leads with its scan, a member's with its
-// cluster's batch-wide rank.  The number of launches and host waits does not depend on the number of scans.
+// value): its front -- the table, the packed batch positions, a lattice per scan inside ONE cell-sorted array of grid
+// positions -- is wm_scan_batch.hpp's, shared with wm_outlier_filter_batch.  A scan's GridDev points at its own slice
+// of cell_start and at the shared array, so a walk never meets a point of another scan, and the union-find, the
+// counters, the two sorts and the outputs run over the whole batch at once: the sort key of a kept root leads with its
+// scan, a member's with its cluster's batch-wide rank.  The number of launches and host waits does not depend on the
+// number of scans.
 #include <limits.h>
 #include <string.h>  // (before rocPRIM's headers, which call memset)
 
 #include "wm_radius_walk.hpp"
+#include "wm_scan_batch.hpp"
 #include "wm_sort.hpp"
-#include "wm_stage.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -48,156 +48,6 @@ namespace {
 constexpr int kLinkBlock = 64;  // queries (threads) of a link workgroup: one wave, as k_outlier_radius
 
 #define WM_UF_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-struct ClScan {  // one scan of a batch
-    const unsigned char *raw;  // its records (device memory)
-    unsigned n, off;           // points; its first batch position
-    unsigned blk0;             // its first workgroup of the kernels over batch positions (kBlock points each)
-    unsigned nf, g0;           // finite points; its first grid position
-    unsigned lblk0;            // its first workgroup of k_cluster_link
-    unsigned long long cell0;  // its first cell
-    GridDev g;                 // its lattice: cell_start = the scan's first cell, pts = the batch's cell-sorted array
-};
-
-// The last scan whose `field` is at or below x.  Scans without points (or without finite points, or without
-// workgroups) share their value with the scan behind them, so the last one found is the one that owns x.
-template <class Field>
-__device__ __forceinline__ unsigned cl_find(const ClScan *__restrict__ tab, unsigned S, unsigned x, Field field) {
-    unsigned k = 0, hi = S;
-    while (hi - k > 1u) {
-        const unsigned mid = (k + hi) >> 1;
-        if (field(tab[mid]) <= x) k = mid;
-        else hi = mid;
-    }
-    return k;
-}
-__device__ __forceinline__ unsigned cl_by_block(const ClScan *tab, unsigned S, unsigned b) {
-    return cl_find(tab, S, b, [](const ClScan &s) { return s.blk0; });
-}
-__device__ __forceinline__ unsigned cl_by_grid(const ClScan *tab, unsigned S, unsigned x) {
-    return cl_find(tab, S, x, [](const ClScan &s) { return s.g0; });
-}
-__device__ __forceinline__ unsigned cl_by_point(const ClScan *tab, unsigned S, unsigned p) {
-    return cl_find(tab, S, p, [](const ClScan &s) { return s.off; });
-}
-
-// float -> unsigned whose unsigned order is the float order (-0.0 canonicalised to +0.0 first)
-__device__ __forceinline__ unsigned cl_orderable(float z) {
-    const unsigned b = __float_as_uint(z == 0.f ? 0.f : z);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// ------------------------------------------------------------------ the front of a batch: pack, boxes, the grid
-// k_pack's conversion into batch positions (.w = the batch position: the scan and the caller's index are recovered
-// from it by the table), and per scan the box and the finite count -- bb: [3 S] minima, [3 S] maxima (orderable),
-// [S] counts.  Minima, maxima and integer sums: the order of the atomics does not matter.
-__global__ void __launch_bounds__(kBlock)
-    k_cluster_pack(const ClScan *__restrict__ tab, unsigned S, size_t stride, float4 *__restrict__ out, unsigned *bb) {
-    __shared__ unsigned s_lo[kBlock / 64][3], s_hi[kBlock / 64][3], s_cnt[kBlock / 64];
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const ClScan me = tab[k];
-    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
-    unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u}, cnt = 0u;
-    if (i < me.n) {
-        const float *q = reinterpret_cast<const float *>(me.raw + (size_t) i * stride);
-        float x = q[0], y = q[1], z = q[2];
-        if (isfinite(x) && isfinite(y) && isfinite(z)) {
-            lo[0] = hi[0] = cl_orderable(x);
-            lo[1] = hi[1] = cl_orderable(y);
-            lo[2] = hi[2] = cl_orderable(z);
-            cnt = 1u;
-        } else {
-            x = y = z = __builtin_nanf("");
-        }
-        out[me.off + i] = make_float4(x, y, z, __uint_as_float(me.off + i));
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        for (int d = 0; d < 3; ++d) {
-            lo[d] = min(lo[d], (unsigned) __shfl_down(lo[d], off));
-            hi[d] = max(hi[d], (unsigned) __shfl_down(hi[d], off));
-        }
-        cnt += __shfl_down(cnt, off);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        for (int d = 0; d < 3; ++d) {
-            s_lo[wave][d] = lo[d];
-            s_hi[wave][d] = hi[d];
-        }
-        s_cnt[wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w) {
-            for (int d = 0; d < 3; ++d) {
-                lo[d] = min(lo[d], s_lo[w][d]);
-                hi[d] = max(hi[d], s_hi[w][d]);
-            }
-            cnt += s_cnt[w];
-        }
-        if (cnt) {
-            for (int d = 0; d < 3; ++d) {
-                atomicMin(&bb[3u * k + d], lo[d]);
-                atomicMax(&bb[3u * S + 3u * k + d], hi[d]);
-            }
-            atomicAdd(&bb[6u * S + k], cnt);
-        }
-    }
-}
-
-__device__ __forceinline__ unsigned cl_cell(const GridDev &g, const float4 &p) {  // (wm_grid.hip: LinearKey)
-    int cx = (int) floorf((p.x - g.ox) * g.inv_h);
-    int cy = (int) floorf((p.y - g.oy) * g.inv_h);
-    int cz = (int) floorf((p.z - g.oz) * g.inv_h);
-    cx = min(max(cx, 0), g.nx - 1);
-    cy = min(max(cy, 0), g.ny - 1);
-    cz = min(max(cz, 0), g.nz - 1);
-    return (unsigned) ((cz * g.ny + cy) * g.nx + cx);
-}
-
-// k_count of wm_grid.hip with the scan's lattice and its first cell; the lane that finds a cell empty counts it as
-// occupied (occ[k]: what build_call_grid's occupancy check fetches, here for every scan at once)
-__global__ void __launch_bounds__(kBlock)
-    k_cluster_count(const ClScan *__restrict__ tab, unsigned S, const float4 *__restrict__ pts, unsigned *__restrict__ cell_of,
-                    unsigned *__restrict__ rank_of, unsigned *counts, unsigned *occ) {
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const ClScan me = tab[k];
-    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
-    unsigned first = 0u;
-    if (i < me.n) {
-        const float4 p = pts[me.off + i];
-        unsigned c = kNoIdx, r = 0u;
-        if (p.x == p.x) {
-            c = cl_cell(me.g, p);
-            r = atomicAdd(&counts[me.cell0 + c], 1u);
-            first = r == 0u ? 1u : 0u;
-        }
-        cell_of[me.off + i] = c;
-        rank_of[me.off + i] = r;
-    }
-    for (int off = 32; off > 0; off >>= 1) first += __shfl_down(first, off);
-    if ((threadIdx.x & 63) == 0 && first) atomicAdd(&occ[k], first);
-}
-
-// k_scatter of wm_grid.hip: the batch's cell-sorted array and the four NaN entries behind its last point
-__global__ void __launch_bounds__(kBlock)
-    k_cluster_scatter(const ClScan *__restrict__ tab, unsigned S, const float4 *__restrict__ pts,
-                      const unsigned *__restrict__ cell_of, const unsigned *__restrict__ rank_of,
-                      const unsigned *__restrict__ cell_start, float4 *__restrict__ out, size_t ncells) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const unsigned end = cell_start[ncells];
-        const float nanv = __builtin_nanf("");
-#pragma unroll
-        for (int u = 0; u < 4; ++u) out[end + u] = make_float4(nanv, nanv, nanv, __uint_as_float(kNoIdx));
-    }
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const ClScan me = tab[k];
-    const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
-    if (i >= me.n) return;
-    const unsigned c = cell_of[me.off + i];
-    if (c == kNoIdx) return;
-    out[cell_start[me.cell0 + c] + rank_of[me.off + i]] = pts[me.off + i];
-}
 
 // ------------------------------------------------------------------ the union-find over grid positions
 // Invariant: parent[x] <= x, and parent[x] is x (x is a root) or an ancestor of x in the forest -- at every moment and
@@ -409,24 +259,21 @@ __global__ void __launch_bounds__(kBlock)
 
 // The context's workspace of the cluster extraction: its own buffers, shared with nothing else on the context.
 struct ClusterWs {
-    DevBuf pts, parent, root_of, min_idx, size, keep, pos, rank_of, lrank_of, size_by_rank, off, labels, offsets, res;
+    DevBuf parent, root_of, min_idx, size, keep, pos, rank_of, lrank_of, size_by_rank, off, labels, offsets, res;
     DevBuf keys_a, keys_b, vals_a, vals_b, sort_tmp;  // the two sorts' ping-pong pairs
     DevBuf idx, pout;                                 // host outputs on their way
-    DevBuf bb, cell_of, counts;                       // a batch's boxes and occupancies, and its counting sort
-    GridLevel grid;
-    PairStage stage;   // a batch's scan table and host clouds up (wm_stage.hpp)
-    PinnedBuf h_res;   // the counters, four per scan; a batch's boxes before them
+    ScanBatchBufs sb;  // the packed cloud and its grid; a batch's front (wm_scan_batch.hpp)
+    PinnedBuf h_res;   // the counters, four per scan
 };
 
 void cluster_release(wm_ctx *ctx) {
     ClusterWs *w = static_cast<ClusterWs *>(ctx->cluster);
     if (!w) return;
-    DevBuf *bufs[] = {&w->pts, &w->parent, &w->root_of, &w->min_idx, &w->size, &w->keep, &w->pos, &w->rank_of,
+    DevBuf *bufs[] = {&w->parent, &w->root_of, &w->min_idx, &w->size, &w->keep, &w->pos, &w->rank_of,
                       &w->lrank_of, &w->size_by_rank, &w->off, &w->labels, &w->offsets, &w->res, &w->keys_a, &w->keys_b,
-                      &w->vals_a, &w->vals_b, &w->sort_tmp, &w->idx, &w->pout, &w->bb, &w->cell_of, &w->counts,
-                      &w->grid.pts, &w->grid.cell_start};
+                      &w->vals_a, &w->vals_b, &w->sort_tmp, &w->idx, &w->pout};
     for (DevBuf *b : bufs) b->release();
-    w->stage.release();
+    w->sb.release();
     w->h_res.release();
     delete w;
     ctx->cluster = nullptr;
@@ -612,7 +459,7 @@ int cl_back(wm_ctx *ctx, ClusterWs &w, ClCall &c) {
             }
         }
         hipLaunchKernelGGL(k_cluster_emit, dim3(blocks_of(n_idx)), dim3(kBlock), 0, st, sorted_pts, (unsigned) n_idx, tab, S,
-                           (const float4 *) w.pts.as<float4>(), idx, d_pout, c.out_stride);
+                           (const float4 *) w.sb.pts.as<float4>(), idx, d_pout, c.out_stride);
         WM_HIP(ctx, hipGetLastError());
         d_idx = idx;
     } else if (!c.host_out && n_idx) {
@@ -667,17 +514,17 @@ int cl_one(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const
     c.offsets_out = offsets_out;
     c.cap_clusters = cap_clusters;
 
-    WM_HIP(ctx, w.pts.reserve(n * sizeof(float4)));
+    WM_HIP(ctx, w.sb.pts.reserve(n * sizeof(float4)));
     if (c.timed) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.pts.as<float4>()));
+    WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.sb.pts.as<float4>()));
     Bbox bb;
     size_t n_finite = 0;
-    WM_TRY(compute_bbox(ctx, w.pts.as<float4>(), n, &bb, &n_finite));
+    WM_TRY(compute_bbox(ctx, w.sb.pts.as<float4>(), n, &bb, &n_finite));
     if (stats) stats->n_finite = n_finite;
     if (n_finite == 0) return cl_nothing_finite(ctx, w, c);
-    WM_TRY(build_call_grid(ctx, w.pts.as<float4>(), n, n_finite, bb,
-                           fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div, &w.grid));
-    c.g = w.grid.d;
+    WM_TRY(build_call_grid(ctx, w.sb.pts.as<float4>(), n, n_finite, bb,
+                           fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div, &w.sb.grid));
+    c.g = w.sb.grid.d;
     c.nf = n_finite;
     c.link_blocks = (unsigned) ((n_finite + kLinkBlock - 1) / kLinkBlock);
     const int rc = cl_back(ctx, w, c);
@@ -687,51 +534,6 @@ int cl_one(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const
     if (stats) cl_stats_out(w.h_res.as<unsigned>(), n_finite, c.ms, stats);
     if (kernel_ms) *kernel_ms = c.ms;
     return rc;
-}
-
-// ------------------------------------------------------------------ a batch's lattices (host)
-uint64_t cl_cells_of(const Bbox &bb, float h) {  // (wm_grid.hip: build_grid_level's lattice)
-    uint64_t c = 1;
-    for (int d = 0; d < 3; ++d) c *= (uint64_t) floor(((double) bb.hi[d] - bb.lo[d]) / h) + 1;
-    return c;
-}
-
-// build_call_grid's automatic cell of a scan (occ == 0) or its second choice from the measured occupancy, under the
-// scan's share of the batch's cells
-float cl_cell_size(const Bbox &bb, size_t n_finite, float floor_h, uint64_t cell_cap, float h_prev, double occ) {
-    float h;
-    if (occ > 0) {
-        h = fmaxf((float) (h_prev * sqrt(3.0 / occ)), floor_h);
-    } else {
-        double vol = 1;
-        for (int d = 0; d < 3; ++d) vol *= fmax((double) bb.hi[d] - bb.lo[d], 1e-3);
-        h = fmaxf((float) fmax(cbrt(vol / (double) n_finite) * 1.5, 1e-4), floor_h);
-    }
-    while (cl_cells_of(bb, h) > cell_cap) h *= 1.26f;
-    return h;
-}
-
-void cl_lattice(const Bbox &bb, float h, GridDev *g) {  // (wm_grid.hip: build_grid_level)
-    g->nx = (int) floor((bb.hi[0] - bb.lo[0]) / h) + 1;
-    g->ny = (int) floor((bb.hi[1] - bb.lo[1]) / h) + 1;
-    g->nz = (int) floor((bb.hi[2] - bb.lo[2]) / h) + 1;
-    const float extent = fmaxf(fmaxf(bb.hi[0] - bb.lo[0], bb.hi[1] - bb.lo[1]), bb.hi[2] - bb.lo[2]);
-    float amax = 0;
-    for (int d = 0; d < 3; ++d) amax = fmaxf(amax, fmaxf(fabsf(bb.lo[d]), fabsf(bb.hi[d])));
-    const float ulp = fmaxf(amax, extent) * 1.2e-7f;
-    g->ox = bb.lo[0];
-    g->oy = bb.lo[1];
-    g->oz = bb.lo[2];
-    g->h = h;
-    g->inv_h = 1.0f / h;
-    g->slack = fmaxf(1e-3f, 8.0f * ulp / h);
-}
-
-float cl_from_orderable(unsigned u) {
-    const unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    float f;
-    memcpy(&f, &b, 4);
-    return f;
 }
 
 }  // namespace
@@ -772,14 +574,12 @@ int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_sc
         !cl_args_ok(p, stride, mem, out_mem) || (unsigned long long) n_scans > WM_CLUSTER_BATCH_MAX_SCANS)
         return WM_ERR_ARG;
     const unsigned S = (unsigned) n_scans;
-    size_t total = 0, cloud_bytes = 0, blocks = 0, max_n = 0;
+    size_t total = 0, max_n = 0;
     for (unsigned k = 0; k < S; ++k) {
         if ((scans[k].n > 0 && !scans[k].pts) || scans[k].n > WM_CLUSTER_BATCH_MAX_POINTS) return WM_ERR_ARG;
         total += scans[k].n;
         if (total > WM_CLUSTER_BATCH_MAX_POINTS) return WM_ERR_ARG;
         max_n = std::max(max_n, scans[k].n);
-        cloud_bytes += align_up256(scans[k].n * stride);
-        blocks += (scans[k].n + kBlock - 1) / kBlock;
     }
     // the sort key of a kept root: the scan, the size, the smallest index -- WM_CLUSTER_BATCH_KEY_BITS in all
     const unsigned field_bits = std::max(bits_of(max_n), 1u);
@@ -804,9 +604,6 @@ int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_sc
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->cluster) ctx->cluster = new ClusterWs();
     ClusterWs &w = *static_cast<ClusterWs *>(ctx->cluster);
-    PairStage &stg = w.stage;
-    hipStream_t st = ctx->stream;
-
     ClCall c;
     c.S = S;
     c.n = total;
@@ -822,107 +619,22 @@ int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_sc
     c.offsets_out = offsets_out;
     c.cap_clusters = cap_clusters;
 
-    // the table's first half and the clouds; pack, the boxes and the finite counts; their fetch
-    const size_t table_bytes = align_up256((size_t) S * sizeof(ClScan));
-    WM_TRY(stg.begin(ctx, table_bytes, cloud_bytes, 0, 0, mem));
-    ClScan *tab = stg.table<ClScan>();
-    unsigned off = 0, blk = 0;
-    for (unsigned k = 0; k < S; ++k) {
-        ClScan &t = tab[k];
-        t = ClScan{};
-        t.n = (unsigned) scans[k].n;
-        t.off = off;
-        t.blk0 = blk;
-        WM_TRY(stg.up.add(ctx, scans[k].pts, scans[k].n * stride, &t.raw));
-        off += t.n;
-        blk += (t.n + kBlock - 1) / kBlock;
-    }
-    c.tab = stg.d_table<ClScan>();
-    WM_HIP(ctx, w.pts.reserve(total * sizeof(float4)));
-    WM_HIP(ctx, w.bb.reserve((size_t) S * 8 * 4));
-    WM_HIP(ctx, w.h_res.reserve((size_t) S * 8 * 4));
-    unsigned *bb = w.bb.as<unsigned>(), *occ = bb + 7 * (size_t) S, *h_bb = w.h_res.as<unsigned>();
-    WM_TRY(stg.submit(ctx));
-    WM_HIP(ctx, hipMemsetAsync(bb, 0xFF, (size_t) S * 3 * 4, st));
-    WM_HIP(ctx, hipMemsetAsync(bb + 3 * (size_t) S, 0, (size_t) S * 5 * 4, st));
-    hipLaunchKernelGGL(k_cluster_pack, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S, stride, w.pts.as<float4>(), bb);
-    WM_HIP(ctx, hipGetLastError());
-    WM_TRY(fast_fetch(ctx, h_bb, bb, (size_t) S * 7 * 4));
-
-    // per scan: the finite count, the box, its grid positions and link workgroups
-    std::vector<Bbox> box(S);
-    std::vector<float> cell(S, 0.f);
-    std::vector<uint64_t> cell_cap(S, 0);
-    const float floor_h = fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div;
-    size_t nf_total = 0, lblk = 0;
-    for (unsigned k = 0; k < S; ++k) {
-        ClScan &t = tab[k];
-        t.nf = h_bb[6 * (size_t) S + k];
-        t.g0 = (unsigned) nf_total;
-        t.lblk0 = (unsigned) lblk;
-        nf_total += t.nf;
-        lblk += (t.nf + kLinkBlock - 1) / kLinkBlock;
-        if (stats) stats[k].n_finite = t.nf;
-        if (!t.nf) continue;
-        for (int d = 0; d < 3; ++d) {
-            box[k].lo[d] = cl_from_orderable(h_bb[3 * (size_t) k + d]);
-            box[k].hi[d] = cl_from_orderable(h_bb[3 * (size_t) S + 3 * (size_t) k + d]);
-        }
-        // the single call's cap is 2^26 + 8 n cells; a batch shares ONE 2^26 among its scans
-        cell_cap[k] = std::min<uint64_t>(8ull * t.n + std::max<uint64_t>(((uint64_t) 1 << 26) / S, 4096), 0x7FFFFFFFull);
-        cell[k] = cl_cell_size(box[k], t.nf, floor_h, cell_cap[k], 0.f, 0.0);
-    }
-    c.nf = nf_total;
-    c.link_blocks = (unsigned) lblk;
-    if (nf_total == 0) return cl_nothing_finite(ctx, w, c);
-
-    // the lattices, cells numbered scan after scan: count, (the occupancies' fetch, at most one recount), scan, scatter
-    WM_HIP(ctx, w.grid.pts.reserve((total + 4) * sizeof(float4)));
-    WM_HIP(ctx, w.cell_of.reserve(2 * total * 4));
-    unsigned *cell_of = w.cell_of.as<unsigned>(), *rank_of = cell_of + total;
-    uint64_t ncells = 0;
-    for (int attempt = 0;; ++attempt) {
-        ncells = 0;
-        for (unsigned k = 0; k < S; ++k) {
-            ClScan &t = tab[k];
-            t.cell0 = ncells;
-            if (!t.nf) continue;
-            cl_lattice(box[k], cell[k], &t.g);
-            ncells += (uint64_t) t.g.nx * t.g.ny * t.g.nz;
-        }
-        // (the stream is idle here -- both fetches have been waited for -- so growing a buffer frees nothing in use)
-        WM_HIP(ctx, w.grid.cell_start.reserve((ncells + 1) * 4));
-        WM_HIP(ctx, w.counts.reserve(ncells * 4));
-        for (unsigned k = 0; k < S; ++k) {
-            tab[k].g.pts = w.grid.pts.as<float4>();
-            tab[k].g.cell_start = w.grid.cell_start.as<unsigned>() + tab[k].cell0;
-        }
-        WM_HIP(ctx, hipMemcpyAsync(stg.up.dev.p, stg.up.host.p, table_bytes, hipMemcpyHostToDevice, st));
-        WM_HIP(ctx, hipMemsetAsync(w.counts.p, 0, ncells * 4, st));
-        hipLaunchKernelGGL(k_cluster_count, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S,
-                           (const float4 *) w.pts.as<float4>(), cell_of, rank_of, w.counts.as<unsigned>(), occ);
-        WM_HIP(ctx, hipGetLastError());
-        if (attempt) break;
-        WM_TRY(fast_fetch(ctx, h_bb, occ, (size_t) S * 4));
-        bool again = false;
-        for (unsigned k = 0; k < S; ++k) {
-            if (!tab[k].nf || !h_bb[k]) continue;
-            const double o = (double) tab[k].nf / h_bb[k];
-            if (o > 6.0 || o < 1.5) {
-                const float h2 = cl_cell_size(box[k], tab[k].nf, floor_h, cell_cap[k], cell[k], o);
-                again = again || h2 != cell[k];
-                cell[k] = h2;
-            }
-        }
-        if (!again) break;
-    }
-    WM_TRY(exclusive_scan(ctx, w.counts.as<unsigned>(), ncells, w.grid.cell_start.as<unsigned>()));
-    hipLaunchKernelGGL(k_cluster_scatter, dim3((unsigned) blocks), dim3(kBlock), 0, st, c.tab, S,
-                       (const float4 *) w.pts.as<float4>(), (const unsigned *) cell_of, (const unsigned *) rank_of,
-                       (const unsigned *) w.grid.cell_start.as<unsigned>(), w.grid.pts.as<float4>(), (size_t) ncells);
-    WM_HIP(ctx, hipGetLastError());
+    // the front (wm_scan_batch.hpp): the table, the packed cloud, the lattices and the cell-sorted array
+    ScanBatch b;
+    WM_TRY(scan_batch_front(ctx, w.sb, scans, S, stride, mem, fminf((float) p->tolerance, 1.0e30f) / ctx->tune_cluster_cell_div,
+                            (unsigned) kLinkBlock,
+                            [&](unsigned k, ClScan &t) {
+                                if (stats) stats[k].n_finite = t.nf;
+                                return true;
+                            },
+                            &b));
+    const ClScan *tab = b.tab;
+    c.tab = b.d_tab;
+    c.nf = b.nf_total;
+    c.link_blocks = (unsigned) b.search_blocks;
+    if (b.nf_total == 0) return cl_nothing_finite(ctx, w, c);
     c.g = GridDev{};
-    c.g.pts = w.grid.pts.as<float4>();
+    c.g.pts = w.sb.grid.pts.as<float4>();
 
     const int rc = cl_back(ctx, w, c);
     if (rc != WM_OK && rc != WM_ERR_ARG) return rc;
