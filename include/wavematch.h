@@ -923,6 +923,87 @@ int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_sc
                              size_t *n_out, wm_cluster_stats *stats /* NULL ok: n_scans entries */,
                              float *kernel_ms /* NULL ok */);
 
+/* ------------------------------------------------------------- plane segmentation (RANSAC) */
+/* pcl::SACSegmentation with a plane model and SAC_RANSAC on the device: one cloud in, one plane and its inliers out.
+ * [PCL-upstream: restated from PCL 1.8 sample_consensus/impl/ransac.hpp (RandomSampleConsensus::computeModel),
+ * sample_consensus/impl/sac_model_plane.hpp (SampleConsensusModelPlane) and segmentation/impl/sac_segmentation.hpp
+ * (SACSegmentation::segment); no PCL on the build machine]  (tests/sac_reference.py is the checker).  All float
+ * arithmetic below is float32 with every operation rounded and nothing fused.
+ *   stream       DEVIATION (PCL draws its samples from rand() / boost): entry j = 0, 1, 2, ... of the hypothesis stream
+ *                is a function of (seed, j, n) alone.  sm64(z), the splitmix64 finaliser, mod 2^64: z ^= z >> 30;
+ *                z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ *                r(j, a, m) = ((sm64(seed + 0x9E3779B97F4A7C15 * (3 j + a + 1)) >> 32) * m) >> 32.
+ *                i0 = r(j, 0, n);  t = r(j, 1, n - 1), i1 = t + (t >= i0);  t = r(j, 2, n - 2), t += (t >= min(i0, i1)),
+ *                t += (t >= max(i0, i1)), i2 = t.  Three distinct indices by construction, no retry loop; n counts
+ *                all records, as PCL's indices do.
+ *   plane        [computeModelCoefficients; DEVIATION: its collinearity test is replaced]  u = p1 - p0, v = p2 - p0,
+ *                c = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x), s = (c.x c.x + c.y c.y) + c.z c.z.
+ *                The entry is SKIPPED iff s is not finite or not > 0 (a non-finite sample, a collinear one, underflow,
+ *                overflow).  Otherwise l = sqrt(s), (a, b, c) = c / l, d = -((a p0.x + b p0.y) + c p0.z).
+ *   axis models  WM_SAC_PERPENDICULAR_PLANE / WM_SAC_PARALLEL_PLANE: ax = the axis normalised in double and rounded to
+ *                float, cos_eps / sin_eps = cos / sin(eps_angle) in double, rounded to float; dot = |(a ax.x + b ax.y)
+ *                + c ax.z|.  PERPENDICULAR (the plane is perpendicular to the axis: its normal along it) is valid iff
+ *                dot >= cos_eps, PARALLEL iff dot < sin_eps.  DEVIATION: PCL goes through acos.  An axis-invalid
+ *                entry is an iteration with count 0 (PCL: countWithinDistance returns 0): while nothing has been
+ *                counted yet, that 0 sets k as in PCL (w = 0, so the loop goes on); DEVIATION: it can never become
+ *                the best model.
+ *   count        [countWithinDistance / selectWithinDistance]  dist = |((a x + b y) + c z) + d|; a point is an inlier
+ *                iff dist < thr, thr = the smallest float not below distance_threshold -- exactly PCL's (double) dist <
+ *                threshold.  A non-finite point is never an inlier (WM_SAC_NONE).
+ *   loop         [computeModel, literally, its quirks included]
+ *                    it = 0; skipped = 0; k = 1.0; best = -1; max_skip = 10 * max_iterations
+ *                    while it < k and skipped < max_skip:
+ *                        take the next entry;  if it is skipped: ++skipped; continue
+ *                        if the entry is axis-valid and count > best:
+ *                            best = count;  w = count / n;  q = clamp(1 - w^3, eps, 1 - eps)   (eps = DBL_EPSILON)
+ *                            k = log(1 - probability) / log(q)
+ *                        else if it is axis-invalid and best == -1:  k = that with w = 0
+ *                        ++it;  if it > max_iterations: break
+ *                so up to max_iterations + 1 entries are evaluated, and an equal count never replaces the best.
+ *                Without a best: WM_NOT_CONVERGED, nothing written, *n_out = 0; n < 3 the same without a device.
+ *   refit        [optimizeModelCoefficients]  iff optimize_coefficients and the model has >= 4 inliers: the plane of
+ *                the inliers' covariance, the eigenvector of its smallest eigenvalue in double, its components
+ *                rounded to float TOWARD ZERO (never longer than the unit vector), d = -normal . centroid with that
+ *                float normal, rounded to nearest; then the inliers are selected again with the refined coefficients
+ *                (SACSegmentation's "Refine inliers").  DEVIATIONS: PCL sums uncentred floats, unusable at UTM offsets -- here the six
+ *                second-order and three first-order sums (PCL's nine accumulators) are formed in double RELATIVE TO
+ *                THE WINNING SAMPLE'S p0 and added exactly, in any order (integer limbs); the eigenvector's sign,
+ *                which PCL leaves open, is fixed to agree with the model's normal; a non-finite result keeps the model.
+ *   output       the inliers' indices ascending.  Every output byte is a function of the input array and the
+ *                parameters; two calls give identical bytes; the model and the counts do not depend on how the stream
+ *                is cut into rounds (option "sac_round"). */
+enum { WM_SAC_PLANE = 0, WM_SAC_PERPENDICULAR_PLANE = 1, WM_SAC_PARALLEL_PLANE = 2 };
+typedef struct {
+    int model;                  /* WM_SAC_* */
+    double distance_threshold;  /* finite and > 0 (PCL's default 0 selects nothing: WM_ERR_ARG here) */
+    int max_iterations;         /* >= 1; PCL's default 50 */
+    double probability;         /* in (0, 1); PCL's default 0.99 */
+    int optimize_coefficients;  /* PCL's default 1 */
+    double axis[3], eps_angle;  /* the two axis models: axis non-zero, 0 < eps_angle <= pi/2, else WM_ERR_ARG */
+    uint64_t seed;              /* extension: PCL has no setter; default 0 */
+} wm_sac_params;
+void wm_sac_default_params(wm_sac_params *p);   /* PCL's: plane, 0 (the threshold must then be set), 50, 0.99, 1 */
+
+enum { WM_SAC_NONE = 0 /* non-finite */, WM_SAC_INLIER = 1, WM_SAC_OUTLIER = 2 };
+typedef struct {
+    size_t n_finite, n_inliers_model /* the winning hypothesis' count */, n_inliers /* returned */;
+    int iterations, skipped, rounds /* device rounds of the stream */, refined /* the refit replaced the model */;
+    long long hypotheses /* stream entries consumed */, best_hypothesis /* its stream index, -1: none */;
+    float model_coefficients[4]; /* the winning hypothesis before the refit */
+    float kernel_ms;             /* pack to the last output */
+} wm_sac_stats;
+
+/* One segmentation over n records of `stride_bytes` (x y z first) in `mem`.  coefficients_out (host): a b c d of the
+ * returned plane.  indices_out (cap entries) and labels_out (n bytes, WM_SAC_*) live in `out_mem`.  More inliers than
+ * `cap`: WM_ERR_ARG with the first `cap` written and *n_out the true count.  Argument errors are found before a device
+ * is touched: a null ctx / p / coefficients_out / n_out, a bad stride, mem or out_mem, n > 0x7FFFFFF0, a null pts with
+ * n > 0, a null indices_out with cap > 0, an unknown model, and the parameter ranges above.  The workspace is the
+ * context's own (freed by wm_ctx_destroy); the registration state and the ground, outlier and cluster workspaces are
+ * not touched. */
+int wm_sac_segment(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, const wm_sac_params *p,
+                   float coefficients_out[4] /* host */, int32_t *indices_out, size_t cap, int out_mem,
+                   size_t *n_out, uint8_t *labels_out /* NULL ok */, wm_sac_stats *stats /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -160,6 +160,23 @@ WM_CLUSTER_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of a cluster_extract_batc
 WM_CLUSTER_BATCH_MAX_SCANS = 0x1000000
 WM_CLUSTER_BATCH_KEY_BITS = 64  # bits(n_scans - 1) + 2 * bits(the largest scan's n), at most
 
+WM_SAC_PLANE, WM_SAC_PERPENDICULAR_PLANE, WM_SAC_PARALLEL_PLANE = 0, 1, 2
+WM_SAC_NONE, WM_SAC_INLIER, WM_SAC_OUTLIER = 0, 1, 2
+
+
+class SacParams(C.Structure):
+    _fields_ = [("model", C.c_int), ("distance_threshold", C.c_double), ("max_iterations", C.c_int),
+                ("probability", C.c_double), ("optimize_coefficients", C.c_int), ("axis", C.c_double * 3),
+                ("eps_angle", C.c_double), ("seed", C.c_uint64)]
+
+
+class SacStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("n_inliers_model", C.c_size_t), ("n_inliers", C.c_size_t),
+                ("iterations", C.c_int), ("skipped", C.c_int), ("rounds", C.c_int), ("refined", C.c_int),
+                ("hypotheses", C.c_longlong), ("best_hypothesis", C.c_longlong), ("model_coefficients", C.c_float * 4),
+                ("kernel_ms", C.c_float)]
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -320,6 +337,11 @@ def lib():
                                                C.POINTER(ClusterParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_size_t), C.POINTER(ClusterStats), C.POINTER(C.c_float)]
+        L.wm_sac_default_params.argtypes = [C.POINTER(SacParams)]
+        L.wm_sac_default_params.restype = None
+        L.wm_sac_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(SacParams),
+                                     C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
+                                     C.c_void_p, C.POINTER(SacStats)]
         _LIB = L
     return _LIB
 
@@ -398,6 +420,18 @@ def cluster_params(params=None, **kw):
         if not hasattr(p, k):
             raise AttributeError(k)
         setattr(p, k, v)
+    return p
+
+
+def sac_params(params=None, **kw):
+    """wm_sac_params from PCL's defaults (wm_sac_default_params), a dict of field values and keywords; `axis` takes
+    any sequence of three numbers."""
+    p = SacParams()
+    lib().wm_sac_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*[float(x) for x in v]) if k == "axis" else v)
     return p
 
 
@@ -758,6 +792,50 @@ class Context:
         out = dict(rc=rc, labels=lab[:n] if labels else None, indices=idx[:m.value], offsets=off[:k.value + 1],
                    n_clusters=k.value, n_out=m.value)
         out.update({f: getattr(st, f) for f, _ in ClusterStats._fields_})
+        return out
+
+    def sac_segment(self, cloud, params=None, labels=True, out_mem=None, cap=None, **kw):
+        """pcl::SACSegmentation with a plane model and RANSAC on the device (wm_sac_segment) -> dict: rc (WM_OK,
+        WM_NOT_CONVERGED without a model, WM_ERR_ARG with more inliers than `cap`), coefficients (4,) float32 (None
+        without a model), indices (the inliers, ascending, int32), labels (n,) uint8 (WM_SAC_NONE / INLIER / OUTLIER;
+        None with labels=False or without a model), n_out and the fields of wm_sac_stats (model_coefficients as a
+        float32 array).  `cloud`: float32 (n, 3|4) numpy array or a HIP torch tensor.  out_mem: where indices and
+        labels are written, WM_MEM_HOST (numpy arrays) or WM_MEM_DEVICE (torch tensors); by default where the cloud
+        lives.  `params`: a SacParams, a dict of its fields, or None (PCL's defaults: the threshold must then come as
+        a keyword); keywords override fields.  cap: room for the indices (default n)."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        if isinstance(params, SacParams):
+            params = {k: (list(params.axis) if k == "axis" else getattr(params, k)) for k, _ in SacParams._fields_}
+        p = sac_params(params, **kw)
+        out_mem = mem if out_mem is None else out_mem
+        cap = n if cap is None else int(cap)
+        m = C.c_size_t(0)
+        st = SacStats()
+        coef = (C.c_float * 4)()
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            lab = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if labels else None
+            idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            lab = np.zeros(max(n, 1), np.uint8) if labels else None
+            idx = np.empty(max(cap, 1), np.int32)
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = lib().wm_sac_segment(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), coef, addr(idx), cap, out_mem,
+                                  C.byref(m), addr(lab), C.byref(st))
+        if rc < 0 and not (rc == WM_ERR_ARG and m.value > cap):  # (more inliers than cap: the caller's to handle)
+            self._check(rc, "wm_sac_segment")
+        found = rc == WM_OK or (rc == WM_ERR_ARG and m.value > cap)
+        out = dict(rc=rc, coefficients=np.array(coef[:], np.float32) if found else None,
+                   indices=idx[:min(m.value, cap)], labels=lab[:n] if labels and found else None, n_out=m.value)
+        out.update({f: getattr(st, f) for f, _ in SacStats._fields_})
+        out["model_coefficients"] = np.array(st.model_coefficients[:], np.float32)
         return out
 
     def cluster_extract_batch(self, clouds, params=None, labels=True, points=False, out_mem=None, **kw):

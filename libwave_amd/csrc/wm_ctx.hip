@@ -235,6 +235,8 @@ const Option kOptions[] = {
     {"outlier_cell_div", "WM_TUNE_OUTLIER_CELL_DIV", nullptr, &wm_ctx::tune_outlier_cell_div, 0.5, 8, 0},
     // cluster extraction (wm_cluster.hip)
     {"cluster_cell_div", "WM_TUNE_CLUSTER_CELL_DIV", nullptr, &wm_ctx::tune_cluster_cell_div, 0.5, 8, 0},
+    // plane segmentation (wm_sac.hip)
+    {"sac_round", "WM_TUNE_SAC_ROUND", &wm_ctx::tune_sac_round, nullptr, 1, 1024, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
     {"ndt_dense", "WM_TUNE_NDT_DENSE", &wm_ctx::tune_ndt_dense, nullptr, kIntMin, kIntMax, 0},
@@ -326,6 +328,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     ground_release(ctx);
     outlier_release(ctx);
     cluster_release(ctx);
+    sac_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

@@ -300,6 +300,8 @@ struct wm_ctx {
     float tune_outlier_cell_div = 2.f;  // the radius filter's grid cell is at least radius / this (0.5 ... 8)
     // cluster extraction (wm_cluster.hip)
     float tune_cluster_cell_div = 2.f;  // the clustering's grid cell is at least tolerance / this (0.5 ... 8)
+    // plane segmentation (wm_sac.hip)
+    int tune_sac_round = 256;    // stream entries a round of the RANSAC loop evaluates at the most (1 ... 1024)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_ndt_dense = 2;      // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice
@@ -330,6 +332,7 @@ struct wm_ctx {
     void *ground = nullptr;                 // wm_ground.hip: the ground filter's workspace (its own, shared with nothing)
     void *outlier = nullptr;                // wm_outlier.hip: the outlier filters' workspace (its own as well)
     void *cluster = nullptr;                // wm_cluster.hip: the cluster extraction's workspace (its own as well)
+    void *sac = nullptr;                    // wm_sac.hip: the plane segmentation's workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -641,6 +644,9 @@ void outlier_release(wm_ctx *ctx);
 
 // ---- wm_cluster.hip
 void cluster_release(wm_ctx *ctx);
+
+// ---- wm_sac.hip
+void sac_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0
