@@ -5,6 +5,7 @@
 #include "wm_icp_step.hpp"
 #include "wm_bins.hpp"
 #include "wm_wave.hpp"
+#include "wm_zigzag.hpp"
 
 namespace wm {
 
@@ -519,32 +520,50 @@ __device__ __forceinline__ unsigned long long scan_box_bal(const GridDev &g, boo
     };
     const bool layered =
         allow_layered && __popcll(__ballot(has && (yb - ya + 1) * (zb - za + 1) > kLayeredRows)) >= 8;
+    // NEAREST FIRST (wm_zigzag.hpp): the layers, and the rows of a layer, are visited outwards from the query's own,
+    // so `best` -- and with it the ball every later row is cut to -- shrinks in the first chunks of a pass instead of
+    // half-way through it (a pass that starts WITHOUT a candidate has one after its first chunks, which is what
+    // lets the first search of a registration walk by layers at all: bottom-up it walked the whole cube), and a
+    // lane is finished as soon as the nearest layer (row) it has left is outside the ball: `best` only shrinks and
+    // what is left only gets farther, so the stop is final.  Lanes that are finished contribute empty rows.
     if (layered) {
+        const int zq = min(max(__float2int_rd(fz), za), zb);
+        // (the stops use the bound of a query ANYWHERE in its cell -- frac 0 -- instead of its own offset: a layer or
+        // a chunk later at most, and two registers fewer in a kernel that has none to spare)
         for (int kz = 0;; ++kz) {
-            const int zz = za + kz;
-            const bool zact = has && zz <= zb;
-            if (__ballot(zact) == 0ull) break;
             const float Rb = ball_r();
             const float lim = Rb + g.slack;
-            const float lim2 = lim * lim, c0 = Rb * Rb + 2.f * g.slack * lim;
+            const float lim2 = lim * lim;
+            const float dz = zigzag_remaining(kz, za, zq, zb, 0.f);
+            const bool zact = has && kz <= zb - za && !(dz * dz > lim2);
+            if (__ballot(zact) == 0ull) break;
+            const int zz = zigzag_coord(kz, za, zq, zb);
             const float rz = fmaxf(fmaxf((float) zz - fz, fz - (float) (zz + 1)), 0.f);
             const float rz2 = rz * rz;
             const float hy = __builtin_amdgcn_sqrtf(fmaxf(lim2 - rz2, 0.f)) * 1.00001f;
             const bool zin = zact && !(rz2 > lim2);
             const int yl = zin ? max(ya, __float2int_rd(fy - hy)) : 1;
             const int yh = zin ? min(yb, __float2int_rd(fy + hy)) : 0;
+            const int yc = min(max(__float2int_rd(fy), yl), yh);  // (an empty layer: yl > yh, no step below is taken)
             const unsigned basez = (unsigned) zz * g.ny * g.nx;
-            for (int yc = yl; __ballot(yc <= yh) != 0ull; yc += RC) {
+            for (int ky = 0;; ky += RC) {
+                // the ball as it is NOW: a chunk's finds cut the next chunk's rows
+                const float Rc = ball_r();
+                const float limc = Rc + g.slack;
+                const float limc2 = limc * limc, c0 = Rc * Rc + 2.f * g.slack * limc;
+                const float dy = zigzag_remaining(ky, yl, yc, yh, 0.f);
+                const bool yact = ky <= yh - yl && !(dy * dy + rz2 > limc2);
+                if (__ballot(yact) == 0ull) break;
                 unsigned a0[RC], a1[RC];
 #pragma unroll
                 for (int u = 0; u < RC; ++u) {
-                    const int yy = yc + u;
+                    const int yy = zigzag_coord(ky + u, yl, yc, yh);
                     const float yf = (float) yy;
                     const float ry = fmaxf(fmaxf(yf - fy, fy - (yf + 1.f)), 0.f);
                     const float rho2 = ry * ry + rz2;
                     const float hx = __builtin_amdgcn_sqrtf(fmaxf(c0 - rho2, 0.f)) * 1.00001f + g.slack;
                     const int xl = max(xa, __float2int_rd(fx - hx)), xh = min(xb, __float2int_rd(fx + hx));
-                    const bool ok = yy <= yh && !(rho2 > lim2) && xl <= xh;
+                    const bool ok = yact && ky + u <= yh - yl && !(rho2 > limc2) && xl <= xh;
                     const unsigned base = basez + (unsigned) yy * g.nx;
                     a0[u] = ok ? base + xl : 0u;
                     a1[u] = ok ? base + xh + 1 : 0u;
