@@ -235,8 +235,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // The sorted member list (batch positions) -> the index inside the member's scan and, for points_out, its x y z as the
-// packed cloud holds them (a member is finite, and a finite point is packed bit for bit) in records of out_stride
-// bytes, the bytes behind z zero.
+// packed cloud holds them (a member is finite, and a finite point is packed bit for bit): cl_write_record.
 __global__ void __launch_bounds__(kBlock)
     k_cluster_emit(const unsigned *__restrict__ sorted, unsigned count, const ClScan *__restrict__ tab, unsigned S,
                    const float4 *__restrict__ pts, int *__restrict__ idx_out, unsigned char *__restrict__ pout,
@@ -245,14 +244,7 @@ __global__ void __launch_bounds__(kBlock)
     if (j >= count) return;
     const unsigned p = sorted[j];
     if (idx_out) idx_out[j] = (int) (tab ? p - tab[cl_by_point(tab, S, p)].off : p);
-    if (pout) {
-        const float4 v = pts[p];
-        unsigned *o = reinterpret_cast<unsigned *>(pout + (size_t) j * out_stride);
-        o[0] = __float_as_uint(v.x);
-        o[1] = __float_as_uint(v.y);
-        o[2] = __float_as_uint(v.z);
-        for (size_t w = 3; w < out_stride / 4; ++w) o[w] = 0u;
-    }
+    if (pout) cl_write_record(pout, j, out_stride, pts[p]);
 }
 
 }  // namespace

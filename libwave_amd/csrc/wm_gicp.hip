@@ -879,18 +879,9 @@ static int launch_cov(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, 
     return WM_OK;
 }
 
-// the neighbour list lives in registers, so its length is a template parameter: the smallest
-// instantiated size >= k keeps both the insertion cost (K compare-swaps per accepted candidate,
-// executed by the whole wave) and the register footprint down
 static int launch_cov_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, const float4 *orig,
                         int k, double eps, double *out, int by_w) {
-    if (k <= 8) return launch_cov<8>(ctx, g, q, n, orig, k, eps, out, by_w);
-    if (k <= 10) return launch_cov<10>(ctx, g, q, n, orig, k, eps, out, by_w);
-    if (k <= 12) return launch_cov<12>(ctx, g, q, n, orig, k, eps, out, by_w);
-    if (k <= 16) return launch_cov<16>(ctx, g, q, n, orig, k, eps, out, by_w);
-    if (k <= 20) return launch_cov<20>(ctx, g, q, n, orig, k, eps, out, by_w);
-    if (k <= 24) return launch_cov<24>(ctx, g, q, n, orig, k, eps, out, by_w);
-    return launch_cov<32>(ctx, g, q, n, orig, k, eps, out, by_w);
+    return knn_ladder(k, [&](auto K) { return launch_cov<decltype(K)::value>(ctx, g, q, n, orig, k, eps, out, by_w); });
 }
 
 // developer / tests (wm_debug_knn): the neighbour lists themselves, as knn_search<K> hands them to k_gicp_cov and
@@ -929,13 +920,7 @@ static int launch_debug_knn(wm_ctx *ctx, const GridDev &g, const float4 *q, size
 
 static int launch_debug_knn_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, size_t n_out, int k, int by_w, int *idx,
                               float *d2) {
-    if (k <= 8) return launch_debug_knn<8>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    if (k <= 10) return launch_debug_knn<10>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    if (k <= 12) return launch_debug_knn<12>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    if (k <= 16) return launch_debug_knn<16>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    if (k <= 20) return launch_debug_knn<20>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    if (k <= 24) return launch_debug_knn<24>(ctx, g, q, n, n_out, k, by_w, idx, d2);
-    return launch_debug_knn<32>(ctx, g, q, n, n_out, k, by_w, idx, d2);
+    return knn_ladder(k, [&](auto K) { return launch_debug_knn<decltype(K)::value>(ctx, g, q, n, n_out, k, by_w, idx, d2); });
 }
 
 // the source's own grid (the target's is the level-0 search grid): what the k-NN of its covariances and normals scans

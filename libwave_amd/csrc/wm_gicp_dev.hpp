@@ -5,6 +5,8 @@
 #pragma once
 #include "wm_internal.hpp"
 
+#include <type_traits>
+
 namespace wm {
 
 constexpr int kGicpAcc = 13;
@@ -214,6 +216,21 @@ __device__ void knn_search(const GridDev &g, float qx, float qy, float qz, int k
         }
         r = fminf(r, rmax);
     }
+}
+
+// The K ladder of the kernels that call knn_search<K> (host).  The neighbour list lives in registers, so its length is
+// a template parameter: the smallest instantiated size >= k keeps both the insertion cost (K compare-swaps per
+// accepted candidate, executed by the whole wave) and the register footprint down.  f gets the rung as a
+// std::integral_constant<int, K> (decltype(K)::value is the template argument) and its result is returned.
+template <class F>
+inline decltype(auto) knn_ladder(int k, F &&f) {
+    if (k <= 8) return f(std::integral_constant<int, 8>{});
+    if (k <= 10) return f(std::integral_constant<int, 10>{});
+    if (k <= 12) return f(std::integral_constant<int, 12>{});
+    if (k <= 16) return f(std::integral_constant<int, 16>{});
+    if (k <= 20) return f(std::integral_constant<int, 20>{});
+    if (k <= 24) return f(std::integral_constant<int, 24>{});
+    return f(std::integral_constant<int, 32>{});
 }
 
 // the covariance PCL's computeCovariances gives a point from its k nearest neighbours (best[0 .. k-1], keys of

@@ -103,13 +103,7 @@ static int launch_normals(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t
 // (the K ladder of the covariance kernel: the smallest instantiated list that holds k)
 static int launch_normals_k(wm_ctx *ctx, const GridDev &g, const float4 *q, size_t n, const float4 *orig, size_t n_orig, int k,
                             float4 *out) {
-    if (k <= 8) return launch_normals<8>(ctx, g, q, n, orig, n_orig, k, out);
-    if (k <= 10) return launch_normals<10>(ctx, g, q, n, orig, n_orig, k, out);
-    if (k <= 12) return launch_normals<12>(ctx, g, q, n, orig, n_orig, k, out);
-    if (k <= 16) return launch_normals<16>(ctx, g, q, n, orig, n_orig, k, out);
-    if (k <= 20) return launch_normals<20>(ctx, g, q, n, orig, n_orig, k, out);
-    if (k <= 24) return launch_normals<24>(ctx, g, q, n, orig, n_orig, k, out);
-    return launch_normals<32>(ctx, g, q, n, orig, n_orig, k, out);
+    return knn_ladder(k, [&](auto K) { return launch_normals<decltype(K)::value>(ctx, g, q, n, orig, n_orig, k, out); });
 }
 
 int plane_normal_k(int k) { return k == 0 ? kPlaneDefaultK : k; }

@@ -69,6 +69,16 @@ __device__ __forceinline__ unsigned cl_orderable(float z) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// Record j of an array of point records of out_stride bytes (a multiple of 4, at least 12): v's x y z as the packed
+// cloud holds them, the bytes behind z zero.
+__device__ __forceinline__ void cl_write_record(unsigned char *pout, size_t j, size_t out_stride, const float4 &v) {
+    unsigned *o = reinterpret_cast<unsigned *>(pout + j * out_stride);
+    o[0] = __float_as_uint(v.x);
+    o[1] = __float_as_uint(v.y);
+    o[2] = __float_as_uint(v.z);
+    for (size_t w = 3; w < out_stride / 4; ++w) o[w] = 0u;
+}
+
 // ------------------------------------------------------------------ the front of a batch: pack, boxes, the grid
 // k_pack's conversion into batch positions (.w = the batch position: the scan and the caller's index are recovered
 // from it by the table), and per scan the box and the finite count -- bb: [3 S] minima, [3 S] maxima (orderable),
