@@ -48,6 +48,30 @@ void SACSegmentation<PointT>::segment(pcl::PointIndices &inliers, pcl::ModelCoef
     }
 }
 
+template <typename PointT>
+void SACSegmentation<PointT>::segmentBatch(const std::vector<PointCloudConstPtr> &clouds, std::vector<pcl::PointIndices> &inliers,
+                                           std::vector<pcl::ModelCoefficients> &coefficients) {
+    static_assert(sizeof(PointT) >= 3 * sizeof(float) && sizeof(PointT) % 4 == 0,
+                  "SACSegmentation: a point type whose first three floats are x, y, z");
+    const size_t count = clouds.size();
+    std::vector<const void *> pts(count, nullptr);
+    std::vector<size_t> n(count, 0);
+    std::vector<unsigned char> null_cloud(count, 0);  // (not vector<bool>: the flags go over as an array)
+    for (size_t k = 0; k < count; ++k) {
+        if (!clouds[k]) {
+            null_cloud[k] = 1;
+            continue;
+        }
+        n[k] = clouds[k]->points.size();
+        if (n[k]) pts[k] = clouds[k]->points.data();
+    }
+    if (!detail::sacSegmentBatch(this->ctx, this->device, pts.data(), n.data(), null_cloud.data(), count, sizeof(PointT),
+                                 this->params, inliers, coefficients)) {
+        inliers.assign(count, pcl::PointIndices());
+        coefficients.assign(count, pcl::ModelCoefficients());
+    }
+}
+
 }  // namespace wave
 
 // PCL_INSTANTIATE_SACSegmentation(MyPoint) in one source file of a program precompiles the class for MyPoint

@@ -5,6 +5,8 @@
 // segment(pcl::PointIndices &, pcl::ModelCoefficients &).  It finds the road, a wall or a table top -- what a caller
 // peels off before clustering.  One segment() is one C-ABI call, wm_sac_segment (include/wavematch.h, which states the
 // rule): hypotheses, counts, refit sums and the inlier list are formed on the device; the host walks PCL's loop.
+// segmentBatch() segments a queue of clouds in ONE C-ABI call, wm_sac_segment_batch: every element equals what
+// segment() gives for that cloud alone.
 //
 // The reference has no such class (its pipelines call PCL's); this one is shaped like
 // wave::EuclideanClusterExtraction<PointT>: the device context is created by the first segment(), so construction needs
@@ -54,6 +56,12 @@ void sacRelease(wm_ctx *&ctx);
 // false (after a LOG_ERROR, both outputs empty) on bad parameters, a cloud without a model or a device error
 bool sacSegment(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride, const SACSegmentationParams &params,
                 pcl::PointIndices &inliers, pcl::ModelCoefficients &coefficients);
+// `count` clouds in one wm_sac_segment_batch call; null_cloud[k] != 0: cloud k was a null pointer (logged, treated as
+// empty).  A cloud without a model gets empty indices and empty values (logged); false: nothing could be run (after a
+// LOG_ERROR, every output empty).  No cloud of three points or more: true without a device.
+bool sacSegmentBatch(wm_ctx *&ctx, int device, const void *const *pts, const size_t *n, const unsigned char *null_cloud,
+                     size_t count, size_t stride, const SACSegmentationParams &params, std::vector<pcl::PointIndices> &inliers,
+                     std::vector<pcl::ModelCoefficients> &coefficients);
 }  // namespace detail
 
 template <typename PointT>
@@ -100,6 +108,13 @@ class SACSegmentation {
 
     // the plane of input_ (wm_sac_segment): its inliers ascending, its four coefficients a b c d
     void segment(pcl::PointIndices &inliers, pcl::ModelCoefficients &model_coefficients);
+
+    // Addition (PCL segments one cloud per call): a queue of clouds in ONE C-ABI call, wm_sac_segment_batch.  Element k
+    // of both outputs equals what segment() gives for clouds[k] alone; a cloud without a model gets empty indices and
+    // empty values; a null cloud is logged and treated as empty; empty vectors are legal.  The input cloud set by
+    // setInputCloud is not used.
+    void segmentBatch(const std::vector<PointCloudConstPtr> &clouds, std::vector<pcl::PointIndices> &inliers,
+                      std::vector<pcl::ModelCoefficients> &coefficients);
 
  private:
     PointCloudConstPtr input_;

@@ -1004,6 +1004,47 @@ int wm_sac_segment(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, 
                    float coefficients_out[4] /* host */, int32_t *indices_out, size_t cap, int out_mem,
                    size_t *n_out, uint8_t *labels_out /* NULL ok */, wm_sac_stats *stats /* NULL ok */);
 
+/* A queue of scans in one device call: the same steps with a scan dimension, one `p` (its seed included), one stride
+ * and one `mem` for the batch (as wm_outlier_filter_batch and wm_cluster_extract_batch), in a number of launches and
+ * host waits that does not depend on n_scans: the front, one round trip per round of the longest-living scan, one for
+ * the refit and one for the offsets.  For every scan k, status[k], coefficients_out + 4 k, the slice [offsets_out[k],
+ * offsets_out[k + 1]) of indices_out (indices local to the scan, ascending), its slice of labels_out (the scans' n
+ * entries one after the other) and stats[k] (but kernel_ms, which is the batch's) EQUAL what wm_sac_segment returns for
+ * that scan alone with the same `p` -- rounds, hypotheses, best_hypothesis, the bits of model_coefficients, refined
+ * and the bits of the refitted coefficients included, whatever the other scans of the batch are and whatever their
+ * order: the hypothesis stream of scan k is a function of (seed, j, n_k), as in the single call.
+ * negative != 0: indices_out / points_out hold the finite points that are NOT inliers of the returned plane, ascending
+ * -- the points the single call labels WM_SAC_OUTLIER.  Labels, coefficients and stats are the same with either
+ * setting; stats[k].n_inliers stays the inliers' number.
+ * points_out (NULL: not wanted): per entry of indices_out the input point's x y z, bit for bit, in records of
+ * out_stride bytes (>= 12, a multiple of 4; the bytes behind z are zero) -- wm_ground_segment_batch's rules, and what
+ * wm_cluster_extract_batch(mem = WM_MEM_DEVICE) takes as it is.  out_mem says where indices_out, points_out and
+ * labels_out live; coefficients_out (4 floats per scan), offsets_out (n_scans + 1 entries), status and stats (n_scans
+ * entries) are host memory.
+ * The call returns WM_OK when the batch ran.  A scan without a model (n < 3, or the all-skipped and all-refused exits)
+ * has status[k] = WM_NOT_CONVERGED and an empty slice with either setting of `negative`; its coefficients are not
+ * written, stats[k] is as the single call leaves it, its slice of labels holds WM_SAC_NONE and carries no meaning.  A
+ * scan with n < 3 costs no device work.  n_scans == 0, or no scan with n >= 3: WM_OK with no device touched, every
+ * offset 0 and every status WM_NOT_CONVERGED (labels_out is then written only where out_mem is WM_MEM_HOST).  More
+ * entries than `cap`: WM_ERR_ARG with the offsets the true ones (the first `cap` indices and points are written).
+ * Argument errors, found before a device is touched: wm_sac_segment's, a null scans / offsets_out / status /
+ * coefficients_out (with n_scans == 0 too), a scan with a null pts and n > 0, a bad out_stride with points_out, a null
+ * indices_out with cap > 0, and a batch beyond the two limits below.  A batch of one scan is the single call.
+ * kernel_ms (NULL ok): device time from the upload to the offsets.  The workspace is the one of wm_sac_segment; the
+ * registration state and the ground, outlier and cluster workspaces are not touched. */
+typedef struct { const void *pts; size_t n; } wm_sac_scan;
+#define WM_SAC_BATCH_MAX_POINTS 0x7FFFFFF0ull /* the scans' points in all, at most */
+#define WM_SAC_BATCH_MAX_SCANS 0x1000000ull   /* n_scans at most */
+int wm_sac_segment_batch(wm_ctx *ctx, const wm_sac_scan *scans, int n_scans, size_t stride_bytes, int mem,
+                         const wm_sac_params *p, int negative,
+                         float *coefficients_out /* host, 4 per scan */,
+                         int32_t *indices_out, size_t cap,
+                         void *points_out /* NULL ok */, size_t out_stride, int out_mem,
+                         size_t *offsets_out /* host, n_scans + 1 entries */,
+                         uint8_t *labels_out /* NULL ok: the scans' n entries one after the other */,
+                         int *status /* host, n_scans entries */, wm_sac_stats *stats /* NULL ok: n_scans entries */,
+                         float *kernel_ms /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

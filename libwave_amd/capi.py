@@ -177,6 +177,14 @@ class SacStats(C.Structure):
                 ("kernel_ms", C.c_float)]
 
 
+class SacScan(C.Structure):
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_size_t)]
+
+
+WM_SAC_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of a sac_segment_batch's scans in all
+WM_SAC_BATCH_MAX_SCANS = 0x1000000
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -342,6 +350,10 @@ def lib():
         L.wm_sac_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(SacParams),
                                      C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
                                      C.c_void_p, C.POINTER(SacStats)]
+        L.wm_sac_segment_batch.argtypes = [C.c_void_p, C.POINTER(SacScan), C.c_int, C.c_size_t, C.c_int, C.POINTER(SacParams),
+                                           C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int),
+                                           C.POINTER(SacStats), C.POINTER(C.c_float)]
         _LIB = L
     return _LIB
 
@@ -837,6 +849,79 @@ class Context:
         out.update({f: getattr(st, f) for f, _ in SacStats._fields_})
         out["model_coefficients"] = np.array(st.model_coefficients[:], np.float32)
         return out
+
+    def sac_segment_batch(self, clouds, params=None, labels=True, points=False, negative=False, out_mem=None, cap=None,
+                          **kw):
+        """sac_segment for a queue of scans in one device call (wm_sac_segment_batch) -> one dict per scan with the
+        keys of sac_segment, each EQUAL to sac_segment's for that scan alone (rc is the scan's status, WM_OK or
+        WM_NOT_CONVERGED; kernel_ms is the batch's) plus `batch_rc`, the call's own return (WM_ERR_ARG with more
+        entries than `cap`: the indices are then the first `cap` of the batch, n_out stays the scan's true count).
+        `clouds`: float32 (n, 3|4) numpy arrays or HIP torch tensors (separate allocations are fine), all of one kind;
+        one `params` for the batch.  negative=True: indices (and points) are the finite points that are NOT inliers;
+        labels, coefficients and the statistics do not change.  out_mem as in sac_segment.  cap: room for the indices
+        of all scans (default: the batch's points).  points=True: -> (that list, kept, offsets) with `kept` the points
+        of all scans' indices, (m, 3|4) float32, scan k's at kept[offsets[k]:offsets[k + 1]] -- in device memory a
+        tensor whose slices cluster_extract_batch takes as they are."""
+        n_scans = len(clouds)
+        if isinstance(params, SacParams):
+            params = {k: (list(params.axis) if k == "axis" else getattr(params, k)) for k, _ in SacParams._fields_}
+        p = sac_params(params, **kw)
+        scans = (SacScan * max(n_scans, 1))()
+        alive, stride, mem, sizes = [], None, None, []
+        for k, cloud in enumerate(clouds):
+            ptr, n, sk, mk, a = _cloud_arg(cloud)
+            assert stride in (None, sk) and mem in (None, mk), "the scans of a batch share one layout and one memory"
+            stride, mem = sk, mk
+            alive.append(a)
+            scans[k].pts, scans[k].n = ptr, n
+            sizes.append(n)
+        stride, mem = stride or 12, WM_MEM_HOST if mem is None else mem
+        out_mem = mem if out_mem is None else out_mem
+        total = sum(sizes)
+        cap = total if cap is None else int(cap)
+        offs = (C.c_size_t * (n_scans + 1))()
+        status = (C.c_int * max(n_scans, 1))()
+        st = (SacStats * max(n_scans, 1))()
+        coef = (C.c_float * (4 * max(n_scans, 1)))()
+        ms = C.c_float(0)
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = clouds[0].device if mem == WM_MEM_DEVICE and n_scans else "cuda:%d" % self.device
+            lab = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev) if labels else None
+            idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            kept = torch.zeros((max(cap, 1), stride // 4), dtype=torch.float32, device=dev) if points else None
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            lab = np.zeros(max(total, 1), np.uint8) if labels else None
+            idx = np.empty(max(cap, 1), np.int32)
+            kept = np.zeros((max(cap, 1), stride // 4), np.float32) if points else None
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = lib().wm_sac_segment_batch(self._h, scans, n_scans, stride, mem, C.byref(p), 1 if negative else 0, coef,
+                                        addr(idx), cap, addr(kept), stride if points else 0, out_mem, offs, addr(lab),
+                                        status, st, C.byref(ms))
+        offs = [int(v) for v in offs]
+        if rc < 0 and not (rc == WM_ERR_ARG and offs[-1] > cap):  # (more entries than cap: the caller's to handle)
+            self._check(rc, "wm_sac_segment_batch")
+        out, at = [], 0
+        for k in range(n_scans):
+            a, b = offs[k], offs[k + 1]
+            found = status[k] == WM_OK
+            d = dict(rc=status[k], batch_rc=rc, coefficients=np.array(coef[4 * k:4 * k + 4], np.float32) if found else None,
+                     indices=idx[min(a, cap):min(b, cap)], labels=lab[at:at + sizes[k]] if labels and found else None,
+                     n_out=b - a)
+            d.update({f: getattr(st[k], f) for f, _ in SacStats._fields_})
+            d["model_coefficients"] = np.array(st[k].model_coefficients[:], np.float32)
+            d["kernel_ms"] = ms.value
+            out.append(d)
+            at += sizes[k]
+        if not points:
+            return out
+        return out, kept[:min(offs[-1], cap)], np.minimum(np.array(offs, np.int64), cap)
 
     def cluster_extract_batch(self, clouds, params=None, labels=True, points=False, out_mem=None, **kw):
         """cluster_extract for a queue of scans in one device call (wm_cluster_extract_batch) -> one dict per scan with

@@ -33,10 +33,10 @@ int sacDefaultDevice() { return shim::defaultDevice(); }
 
 void sacRelease(wm_ctx *&ctx) { shim::release(ctx); }
 
-bool sacSegment(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride, const SACSegmentationParams &params,
-                pcl::PointIndices &inliers, pcl::ModelCoefficients &coefficients) {
-    inliers.indices.clear();
-    coefficients.values.clear();
+namespace {
+
+// the C ABI's parameters of `params`; false (after a LOG_ERROR): a method or model that is not built
+bool sacParams(const SACSegmentationParams &params, wm_sac_params *out) {
     if (params.method_type != pcl::SAC_RANSAC) {
         LOG_ERROR("SACSegmentation: only SAC_RANSAC is built (method type %d)", params.method_type);
         return false;
@@ -56,6 +56,18 @@ bool sacSegment(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stri
     for (int k = 0; k < 3; ++k) p.axis[k] = params.axis[k];
     p.eps_angle = params.eps_angle;
     p.seed = params.seed;
+    *out = p;
+    return true;
+}
+
+}  // namespace
+
+bool sacSegment(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stride, const SACSegmentationParams &params,
+                pcl::PointIndices &inliers, pcl::ModelCoefficients &coefficients) {
+    inliers.indices.clear();
+    coefficients.values.clear();
+    wm_sac_params p;
+    if (!sacParams(params, &p)) return false;
     if (!shim::acquire(ctx, device)) return false;
     std::vector<int32_t> indices(n);
     float coef[4] = {0, 0, 0, 0};
@@ -69,6 +81,55 @@ bool sacSegment(wm_ctx *&ctx, int device, const void *pts, size_t n, size_t stri
     }
     inliers.indices.assign(indices.begin(), indices.begin() + n_out);
     coefficients.values.assign(coef, coef + 4);
+    return true;
+}
+
+bool sacSegmentBatch(wm_ctx *&ctx, int device, const void *const *pts, const size_t *n, const unsigned char *null_cloud,
+                     size_t count, size_t stride, const SACSegmentationParams &params, std::vector<pcl::PointIndices> &inliers,
+                     std::vector<pcl::ModelCoefficients> &coefficients) {
+    inliers.assign(count, pcl::PointIndices());
+    coefficients.assign(count, pcl::ModelCoefficients());
+    wm_sac_params p;
+    if (!sacParams(params, &p)) return false;
+    std::vector<wm_sac_scan> scans(count);
+    size_t total = 0;
+    bool any = false;
+    for (size_t k = 0; k < count; ++k) {
+        if (null_cloud[k]) LOG_ERROR("segmentBatch: cloud %zu is a null pointer", k);
+        scans[k].pts = pts[k];
+        scans[k].n = n[k];
+        total += n[k];
+        any = any || n[k] >= 3;
+    }
+    if (count > WM_SAC_BATCH_MAX_SCANS) {
+        LOG_ERROR("segmentBatch: too many clouds");
+        return false;
+    }
+    if (!any) {  // (no cloud has a sample: no device is opened; as segment() for each alone)
+        for (size_t k = 0; k < count; ++k)
+            if (!null_cloud[k]) LOG_ERROR("wm_sac_segment_batch: cloud %zu: no model found", k);
+        return true;
+    }
+    if (!shim::acquire(ctx, device)) return false;
+    std::vector<int32_t> idx(total);
+    std::vector<float> coef(4 * count, 0.f);
+    std::vector<size_t> offsets(count + 1, 0);
+    std::vector<int> status(count, WM_NOT_CONVERGED);
+    const int rc = wm_sac_segment_batch(ctx, scans.data(), static_cast<int>(count), stride, WM_MEM_HOST, &p, 0, coef.data(),
+                                        idx.data(), total, nullptr, 0, WM_MEM_HOST, offsets.data(), nullptr, status.data(),
+                                        nullptr, nullptr);
+    if (rc != WM_OK) {
+        LOG_ERROR("wm_sac_segment_batch failed: %s [%s]", wm_strerror(rc), wm_last_error(ctx));
+        return false;
+    }
+    for (size_t k = 0; k < count; ++k) {
+        if (status[k] != WM_OK) {  // (as segment() for that cloud alone: logged, both outputs empty)
+            if (!null_cloud[k]) LOG_ERROR("wm_sac_segment_batch: cloud %zu: no model found", k);
+            continue;
+        }
+        inliers[k].indices.assign(idx.begin() + offsets[k], idx.begin() + offsets[k + 1]);
+        coefficients[k].values.assign(coef.begin() + 4 * k, coef.begin() + 4 * k + 4);
+    }
     return true;
 }
 
