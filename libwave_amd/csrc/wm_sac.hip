@@ -10,22 +10,28 @@
 // discarded.  A round never holds more entries than the loop can still count as iterations (max_iterations + 1 - it):
 // only skipped entries make another round necessary.  How the stream is cut into rounds changes no output.
 //
-// Launches of a single call: pack, then per round
-//   k_sac_hypotheses   one lane per stream entry: indices -> three point loads -> plane -> validity; a float4 and a flag
-//   k_sac_count        the hot kernel: a lane keeps kSacPts points in registers and loops over the round's planes, read
-//                      through a wave-uniform index (scalar loads); per plane a ballot and a popcount per point slot,
-//                      accumulated per workgroup in LDS; one integer atomicAdd per plane and workgroup at its end.
-//                      Integer counts: order-independent.  The points are read once per round.
-//   one fetch of the round (planes, flags, counts)
-// and behind the loop k_sac_sums (the refit's nine sums of the model's inliers as exact integer limbs, wm_bins.hpp's
-// splitting with a bins array of this call's own) + one fetch of the limbs, the 3 x 3 eigenproblem on the host, then
-// k_sac_select (flags and labels) -> exclusive_scan -> k_sac_compact and one fetch of the count.
-//
-// A batch (sac_batch below) runs the same device functions with a scan dimension: wm_scan_table.hpp's table and pack,
-// per round a small table of the LIVE scans (each with its own j0 and R), one hypotheses launch over all entries of the
-// round, one count launch whose workgroups are bound to ONE scan each, one fetch of the (flag, count) pairs; behind the
-// rounds the models are recomputed from their stream entries, the refit's bins are summed on the device in the single
-// call's order, and one select / scan / compact covers the batch.
+// ONE set of kernels and one host back (sac_call) serve both entry points, as in wm_ground.hip, wm_outlier.hip and
+// wm_cluster.hip: the scans reach the kernels as a device table, or as tab == nullptr and the one scan by value in the
+// kernel arguments (the single call: no table, no staging, nothing uploaded).  So every byte of scan k of a batch EQUALS
+// the single call's for that scan alone -- `rounds` and the refit's bits included -- because the same code made it.
+//   front      the single call: pack_cloud.  A batch: wm_scan_table.hpp's table and pack into batch positions.
+//   a round    a row (SacRow) per LIVE scan, each with its own j0 and R: the batch's rows go up as a small table, the
+//              single call's one row travels in the kernel arguments (SacRows).
+//     k_sac_hypotheses   one lane per stream entry of the round, over all rows: indices -> three point loads -> plane ->
+//                        validity; a float4 and a flag
+//     k_sac_count        the hot kernel; its workgroups are bound to ONE row each.  A lane keeps kSacPts points in
+//                        registers and loops over the row's planes, read through a wave-uniform index (scalar loads);
+//                        per plane a ballot and a popcount per point slot, accumulated per workgroup in LDS; one integer
+//                        atomicAdd per plane and workgroup at its end.  Integer counts: order-independent.  The points
+//                        are read once per round.
+//     one fetch of the round's (flag, count) pairs, 8 bytes an entry; the first round's has the finite counts in front
+//   behind the rounds (SacScans: the scan table with a SacFin per scan, or one of each by value)
+//     k_sac_models       a lane per scan: the model is entry best_j of the scan's stream, evaluated again
+//     k_sac_sums         where a scan is refitted: the nine sums of the model's inliers as exact integer limbs
+//                        (wm_bins.hpp's splitting) in bins of the call's own; k_sac_bins_sums adds a scan's bins in one
+//                        fixed order.  One fetch of a SacOut per scan, the 3 x 3 eigenproblem on the host
+//     k_sac_select (flags and labels) -> exclusive_scan -> k_sac_compact, and one fetch of the offsets.  A call
+//                        without a refit reads the models from the device and has them back with this fetch.
 #include <float.h>
 #include <string.h>
 
@@ -52,7 +58,6 @@ constexpr int kSacBins = 256;
 constexpr int kSacStride = 16;
 constexpr int kSacPoison = kSacStride - 1;
 constexpr int kSacBinSize = kBinLimbs * kSacStride;  // words of a bin
-constexpr size_t kSacBinWords = (size_t) kSacBins * kSacBinSize;
 
 // ------------------------------------------------------------------ the hypothesis stream (host and device)
 WM_HD unsigned long long sac_sm64(unsigned long long z) {
@@ -92,7 +97,7 @@ struct SacAxis {
 // ------------------------------------------------------------------ the steps both entry points run (device)
 // Entry j of the stream of a cloud of n points: its plane and its flag (a skipped entry's plane is zero).  Every
 // operation is rounded and sqrt and the division are the correctly rounded ones, so the plane is a function of the
-// entry -- wherever it is evaluated (a round's lane; the lane that recomputes a batch's models).
+// entry -- wherever it is evaluated (a round's lane; the lane that recomputes a scan's model behind the rounds).
 __device__ __forceinline__ unsigned sac_hypothesis(const float4 *__restrict__ pts, unsigned n, unsigned long long seed,
                                                    unsigned long long j, const SacAxis &ax, float4 &pl) {
     unsigned i[3];
@@ -199,82 +204,7 @@ __device__ __forceinline__ void sac_sums_wave(bool in, const float4 &p, const fl
         (void) __hip_atomic_fetch_add(b + kSacPoison, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Component c of a cloud's sums from its first `nbins` bins: the bins' values (bins_value: the same double on the host
-// and on the device) added in DOUBLE, bin 0 first, every add rounded.  The refit's bits depend on which wave fed which
-// bin and on this order, so both entry points sum here.  A bin that no wave fed is +0.0 and changes no sum: a cloud of
-// fewer than kSacBins waves needs only its waves' bins.
-__device__ __host__ inline double sac_bins_sum(const long long *bins, unsigned nbins, int c) {
-    double s = 0.0;
-    for (unsigned b = 0; b < nbins; ++b) {  // (a bin's limbs are exact integers: its value is a function of the inliers)
-        const long long *w = bins + (size_t) b * kSacBinSize + c;
-        s += bins_value(w[0], w[kSacStride], w[2 * kSacStride]);
-    }
-    return s;
-}
-
-// ------------------------------------------------------------------ the single call's kernels
-// One lane per entry j0 + e of the round.  counts[e] = 0 for the count kernel behind it.
-__global__ void __launch_bounds__(kBlock)
-    k_sac_hypotheses(const float4 *__restrict__ pts, unsigned n, unsigned long long seed, unsigned long long j0, unsigned R,
-                     SacAxis ax, float4 *__restrict__ planes, unsigned *__restrict__ flags, unsigned *__restrict__ counts) {
-    const unsigned e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= R) return;
-    float4 pl;
-    const unsigned flag = sac_hypothesis(pts, n, seed, j0 + e, ax, pl);
-    planes[e] = pl;
-    flags[e] = flag;
-    counts[e] = 0u;
-}
-
-// The hot kernel (sac_count_tiles): the grid's workgroups share the cloud.  finite_out: the first round's.
-__global__ void __launch_bounds__(kBlock)
-    k_sac_count(const float4 *__restrict__ pts, unsigned n, const float4 *__restrict__ planes,
-                const unsigned *__restrict__ flags, unsigned R, float thr, unsigned *__restrict__ counts,
-                unsigned *__restrict__ finite_out) {
-    sac_count_tiles(pts, n, planes, flags, R, thr, counts, blockIdx.x, gridDim.x, finite_out);
-}
-
-// The refit's sums over the MODEL's inliers, relative to p0 = pts[i0] (the winning sample's first point, finite since
-// its entry was valid); bin = the wave's number mod kSacBins.  tail: the words behind the bins, where p0 goes for the host.
-__global__ void __launch_bounds__(kBlock)
-    k_sac_sums(const float4 *__restrict__ pts, unsigned n, float4 pl, float thr, unsigned i0, long long *__restrict__ bins,
-               float4 *__restrict__ tail) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    const float4 p0 = pts[i0];
-    if (i == 0u) *tail = p0;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool in = false;
-    if (i < n) {
-        p = pts[i];
-        in = sac_dist(pl, p.x, p.y, p.z) < thr;
-    }
-    const unsigned wave = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    sac_sums_wave(in, p, p0, bins + (size_t) (wave % kSacBins) * kSacBinSize);
-}
-
-// caller order: the scan's input (1: an inlier of the returned plane) and the label
-__global__ void __launch_bounds__(kBlock)
-    k_sac_select(const float4 *__restrict__ pts, unsigned n, float4 pl, float thr, unsigned *__restrict__ flag,
-                 unsigned char *__restrict__ labels) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pts[i];
-    const bool in = sac_dist(pl, p.x, p.y, p.z) < thr;
-    flag[i] = in ? 1u : 0u;
-    if (labels) labels[i] = (unsigned char) (in ? WM_SAC_INLIER : p.x == p.x ? WM_SAC_OUTLIER : WM_SAC_NONE);
-}
-
-// pos = the exclusive scan of flag (n + 1 entries): the inliers' indices ascending, the first `cap` of them
-__global__ void __launch_bounds__(kBlock)
-    k_sac_compact(const unsigned *__restrict__ flag, const unsigned *__restrict__ pos, unsigned n, unsigned cap,
-                  int *__restrict__ idx_out) {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const unsigned at = pos[i];
-    if (at < cap) idx_out[at] = (int) i;
-}
-
-// ------------------------------------------------------------------ a batch's kernels
+// ------------------------------------------------------------------ the kernels of a round
 struct SacRow {  // a live scan in a round
     unsigned long long j0;  // its first stream entry of the round
     unsigned scan, R;       // the scan; its entries of the round (>= 1)
@@ -283,10 +213,49 @@ struct SacRow {  // a live scan in a round
     unsigned nb, pad;       // its count workgroups (>= 1)
 };
 
+// The rows of a round: a table in device memory (a batch), or tab == nullptr and the one row by value (the single call:
+// entry 0, workgroup 0 and position 0 are its own).  at(x, field): the row that owns entry or workgroup x.
+struct SacRows {
+    const SacRow *tab;
+    unsigned L;
+    SacRow one;
+    template <class Field>
+    __device__ __forceinline__ SacRow at(unsigned x, Field field) const {
+        if (tab) return tab[cl_find(tab, L, x, field)];
+        return one;
+    }
+};
+
+// One lane per entry of the round (E of them), over all rows.  counts[e] = 0 for the count kernel behind it.
+__global__ void __launch_bounds__(kBlock)
+    k_sac_hypotheses(const float4 *__restrict__ pts, SacRows rows, unsigned E, unsigned long long seed, SacAxis ax,
+                     float4 *__restrict__ planes, unsigned *__restrict__ flags, unsigned *__restrict__ counts) {
+    const unsigned e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= E) return;
+    const SacRow me = rows.at(e, [](const SacRow &r) { return r.e0; });
+    float4 pl;
+    const unsigned flag = sac_hypothesis(pts + me.off, me.n, seed, me.j0 + (e - me.e0), ax, pl);
+    planes[e] = pl;
+    flags[e] = flag;
+    counts[e] = 0u;
+}
+
+// The hot kernel (sac_count_tiles).  A workgroup is bound to tiles of ONE row: the LDS counters and the one atomic per
+// plane and workgroup are that scan's.  finite_out: the single call's first round counts its finite points here (a
+// batch has them from the pack).
+__global__ void __launch_bounds__(kBlock)
+    k_sac_count(const float4 *__restrict__ pts, SacRows rows, const float4 *__restrict__ planes,
+                const unsigned *__restrict__ flags, float thr, unsigned *__restrict__ counts, unsigned *__restrict__ finite_out) {
+    const SacRow me = rows.at(blockIdx.x, [](const SacRow &r) { return r.cb0; });
+    sac_count_tiles(pts + me.off, me.n, planes + me.e0, flags + me.e0, me.R, thr, counts + me.e0, blockIdx.x - me.cb0, me.nb,
+                    finite_out);
+}
+
+// ------------------------------------------------------------------ the kernels behind the rounds
 struct SacFin {  // a scan behind the rounds
     long long best_j;       // its model's stream entry, -1: no model
     unsigned refit, bin0;   // whether its sums are formed; its first bin
-    unsigned nbins, has;    // min(kSacBins, its waves); whether `coef` holds its returned plane (the selection)
+    unsigned nbins, has;    // min(kSacBins, its waves); whether `coef` holds its returned plane (else: SacOut's model)
     unsigned pad[2];
     float4 coef;
 };
@@ -297,41 +266,35 @@ struct SacOut {  // what the host needs of a scan behind the rounds
     unsigned poison, pad[3];
 };
 
-// One lane per entry of the round, over all live scans.
-__global__ void __launch_bounds__(kBlock)
-    k_sac_hypotheses_batch(const float4 *__restrict__ pts, const SacRow *__restrict__ rows, unsigned L, unsigned E,
-                           unsigned long long seed, SacAxis ax, float4 *__restrict__ planes, unsigned *__restrict__ flags,
-                           unsigned *__restrict__ counts) {
-    const unsigned e = blockIdx.x * kBlock + threadIdx.x;
-    if (e >= E) return;
-    const SacRow me = rows[cl_find(rows, L, e, [](const SacRow &r) { return r.e0; })];
-    float4 pl;
-    const unsigned flag = sac_hypothesis(pts + me.off, me.n, seed, me.j0 + (e - me.e0), ax, pl);
-    planes[e] = pl;
-    flags[e] = flag;
-    counts[e] = 0u;
-}
+// The scans of a call behind the rounds: the scan table and a SacFin per scan in device memory (a batch), or
+// tab == nullptr and the one scan with its SacFin by value (the single call; a look-up in a table of one never reads
+// the table, cl_find).  Of a ClScan only n, off, blk0 and aux0 (the scan's first label) are read.
+struct SacScans {
+    const ClScan *tab;
+    const SacFin *fins;
+    unsigned S;
+    ClScan one;
+    SacFin fin1;
+    __device__ __forceinline__ ClScan scan(unsigned k) const {
+        if (tab) return tab[k];
+        return one;
+    }
+    __device__ __forceinline__ SacFin fin(unsigned k) const {
+        if (tab) return fins[k];
+        return fin1;
+    }
+};
 
-// A workgroup is bound to tiles of ONE scan: the LDS counters and the one atomic per plane and workgroup are the scan's.
+// One lane per scan: the model is entry best_j of the scan's stream, evaluated again, and p0 its sample's first point
+// (finite, since the entry was valid).
 __global__ void __launch_bounds__(kBlock)
-    k_sac_count_batch(const float4 *__restrict__ pts, const SacRow *__restrict__ rows, unsigned L,
-                      const float4 *__restrict__ planes, const unsigned *__restrict__ flags, float thr,
-                      unsigned *__restrict__ counts) {
-    const SacRow me = rows[cl_find(rows, L, blockIdx.x, [](const SacRow &r) { return r.cb0; })];
-    sac_count_tiles(pts + me.off, me.n, planes + me.e0, flags + me.e0, me.R, thr, counts + me.e0, blockIdx.x - me.cb0, me.nb,
-                    nullptr);
-}
-
-// One lane per scan: the model is entry best_j of the scan's stream, evaluated again, and p0 its sample's first point.
-__global__ void __launch_bounds__(kBlock)
-    k_sac_models(const ClScan *__restrict__ tab, const SacFin *__restrict__ fin, unsigned S, const float4 *__restrict__ pts,
-                 unsigned long long seed, SacAxis ax, SacOut *__restrict__ out) {
+    k_sac_models(SacScans sc, const float4 *__restrict__ pts, unsigned long long seed, SacAxis ax, SacOut *__restrict__ out) {
     const unsigned k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= S) return;
+    if (k >= sc.S) return;
     float4 pl = make_float4(0.f, 0.f, 0.f, 0.f), p0 = pl;
-    const long long bj = fin[k].best_j;
+    const long long bj = sc.fin(k).best_j;
     if (bj >= 0) {
-        const ClScan me = tab[k];
+        const ClScan me = sc.scan(k);
         (void) sac_hypothesis(pts + me.off, me.n, seed, (unsigned long long) bj, ax, pl);
         unsigned i[3];
         sac_sample(seed, (unsigned long long) bj, me.n, i);
@@ -342,15 +305,16 @@ __global__ void __launch_bounds__(kBlock)
     out[k].poison = 0u;
 }
 
-// k_sac_sums over batch positions.  The workgroups are aligned to each scan's start (blk0), so a wave's number INSIDE
-// its scan mod kSacBins is its bin, exactly as in the single call; the scan's bins start at bin0.
+// The refit's sums over the MODEL's inliers, relative to p0, over batch positions.  The workgroups are aligned to each
+// scan's start (blk0), so a wave's number INSIDE its scan mod kSacBins is its bin, whatever else is in the call; the
+// scan's bins start at bin0.
 __global__ void __launch_bounds__(kBlock)
-    k_sac_sums_batch(const ClScan *__restrict__ tab, unsigned S, const SacFin *__restrict__ fin, const SacOut *__restrict__ out,
-                     const float4 *__restrict__ pts, float thr, long long *__restrict__ bins) {
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const SacFin f = fin[k];
+    k_sac_sums(SacScans sc, const SacOut *__restrict__ out, const float4 *__restrict__ pts, float thr,
+               long long *__restrict__ bins) {
+    const unsigned k = cl_by_block(sc.tab, sc.S, blockIdx.x);
+    const SacFin f = sc.fin(k);
     if (!f.refit) return;  // (the whole workgroup)
-    const ClScan me = tab[k];
+    const ClScan me = sc.scan(k);
     const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
     const float4 pl = out[k].model, p0 = out[k].p0;
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -363,34 +327,51 @@ __global__ void __launch_bounds__(kBlock)
     sac_sums_wave(in, p, p0, bins + ((size_t) f.bin0 + wave % kSacBins) * kSacBinSize);
 }
 
-// A wave per scan: its bins into the nine doubles (lane c: component c, sac_bins_sum) and the poison flag.
-__global__ void __launch_bounds__(64)
-    k_sac_bins_sums(const SacFin *__restrict__ fin, const long long *__restrict__ bins, SacOut *__restrict__ out) {
+// A workgroup per scan: its bins into the nine doubles and the poison flag.  Thread b turns bin b's limbs into their
+// values (bins_value: a bin's limbs are exact integers, so its value is a function of the inliers); thread c then adds
+// component c's values in DOUBLE, bin 0 first, every add rounded.  The refit's bits depend on which wave fed which bin
+// and on this order: tests/test_sac_pinned_gpu.py holds them to a record.  A bin that no wave fed is +0.0 and changes
+// no sum: a scan of fewer than kSacBins waves has only its waves' bins.
+__global__ void __launch_bounds__(kSacBins)
+    k_sac_bins_sums(SacScans sc, const long long *__restrict__ bins, SacOut *__restrict__ out) {
+    __shared__ double s_val[kSacComps][kSacBins];
+    __shared__ unsigned s_poison;
     const unsigned k = blockIdx.x;
-    const SacFin f = fin[k];
-    if (!f.refit) return;
-    const long long *b = bins + (size_t) f.bin0 * kSacBinSize;
-    if (threadIdx.x < (unsigned) kSacComps) out[k].sum[threadIdx.x] = sac_bins_sum(b, f.nbins, (int) threadIdx.x);
-    bool poison = false;
-    for (unsigned j = threadIdx.x; j < f.nbins; j += 64u) poison = poison || b[(size_t) j * kSacBinSize + kSacPoison] != 0ll;
-    const bool any = __ballot(poison) != 0ull;
-    if (threadIdx.x == 0u) out[k].poison = any ? 1u : 0u;
+    const SacFin f = sc.fin(k);
+    if (!f.refit) return;  // (the whole workgroup)
+    if (threadIdx.x == 0u) s_poison = 0u;
+    __syncthreads();
+    if (threadIdx.x < f.nbins) {
+        const long long *w = bins + ((size_t) f.bin0 + threadIdx.x) * kSacBinSize;
+#pragma unroll
+        for (int c = 0; c < kSacComps; ++c) s_val[c][threadIdx.x] = bins_value(w[c], w[kSacStride + c], w[2 * kSacStride + c]);
+        if (w[kSacPoison] != 0ll) s_poison = 1u;  // (every writer writes 1)
+    }
+    __syncthreads();
+    if (threadIdx.x < (unsigned) kSacComps) {
+        double s = 0.0;
+#pragma unroll 8
+        for (unsigned b = 0; b < f.nbins; ++b) s += s_val[threadIdx.x][b];
+        out[k].sum[threadIdx.x] = s;
+    }
+    if (threadIdx.x == 0u) out[k].poison = s_poison;
 }
 
-// k_sac_select over batch positions with the scans' returned planes.  flag: inlier, or with `negative` finite
-// non-inlier; a scan without a model keeps nothing and its labels are NONE.  labels: the scans' n entries one after the
-// other (aux0: the scan's first label).  ninl != nullptr: the scans' inliers are counted (integers).
+// The selection over batch positions with the scans' returned planes: the refit's, or where the call has no refit the
+// model as k_sac_models left it.  flag: inlier, or with `negative` finite non-inlier; a scan without a model keeps
+// nothing and its labels are NONE.  labels: the scans' n entries one after the other (aux0: the scan's first label).
+// ninl != nullptr: the scans' inliers are counted (integers).
 __global__ void __launch_bounds__(kBlock)
-    k_sac_select_batch(const ClScan *__restrict__ tab, unsigned S, const SacFin *__restrict__ fin, const float4 *__restrict__ pts,
-                       float thr, int negative, unsigned *__restrict__ flag, unsigned char *__restrict__ labels,
-                       unsigned *__restrict__ ninl) {
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const ClScan me = tab[k];
+    k_sac_select(SacScans sc, const SacOut *__restrict__ out, const float4 *__restrict__ pts, float thr, int negative,
+                 unsigned *__restrict__ flag, unsigned char *__restrict__ labels, unsigned *__restrict__ ninl) {
+    const unsigned k = cl_by_block(sc.tab, sc.S, blockIdx.x);
+    const ClScan me = sc.scan(k);
+    const SacFin f = sc.fin(k);
     const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
-    const bool has = fin[k].has != 0u;
+    const bool has = f.best_j >= 0;
     bool in = false, finite = false;
     if (i < me.n) {
-        const float4 pl = fin[k].coef;
+        const float4 pl = f.has ? f.coef : out[k].model;
         const float4 p = pts[me.off + i];
         finite = p.x == p.x;
         in = has && sac_dist(pl, p.x, p.y, p.z) < thr;
@@ -409,15 +390,13 @@ __global__ void __launch_bounds__(kBlock)
 // entries: the index INSIDE the scan and, where wanted, the point's record; the grid's first S + 1 threads write the
 // scans' offsets.
 __global__ void __launch_bounds__(kBlock)
-    k_sac_compact_batch(const ClScan *__restrict__ tab, unsigned S, unsigned blocks, unsigned total,
-                        const float4 *__restrict__ pts, const unsigned *__restrict__ flag, const unsigned *__restrict__ pos,
-                        int *__restrict__ idx_out, size_t cap, unsigned char *__restrict__ pout, size_t out_stride,
-                        unsigned *__restrict__ offs) {
+    k_sac_compact(SacScans sc, unsigned blocks, unsigned total, const float4 *__restrict__ pts,
+                  const unsigned *__restrict__ flag, const unsigned *__restrict__ pos, int *__restrict__ idx_out, size_t cap,
+                  unsigned char *__restrict__ pout, size_t out_stride, unsigned *__restrict__ offs) {
     const size_t g = (size_t) blockIdx.x * kBlock + threadIdx.x;
-    if (g <= S) offs[g] = pos[g < S ? tab[g].off : total];
+    if (g <= sc.S) offs[g] = pos[g < sc.S ? sc.scan((unsigned) g).off : total];
     if (blockIdx.x >= blocks) return;
-    const unsigned k = cl_by_block(tab, S, blockIdx.x);
-    const ClScan me = tab[k];
+    const ClScan me = sc.scan(cl_by_block(sc.tab, sc.S, blockIdx.x));
     const unsigned i = (blockIdx.x - me.blk0) * kBlock + threadIdx.x;
     if (i >= me.n || !flag[me.off + i]) return;
     const unsigned at = pos[me.off + i];
@@ -432,27 +411,27 @@ unsigned blocks_of(size_t n) { return (unsigned) ((n + kBlock - 1) / kBlock); }
 
 // The context's workspace of the plane segmentation: its own buffers, shared with nothing else on the context.
 struct SacWs {
-    DevBuf pts;            // the packed cloud; a batch: the packed clouds, batch positions
-    DevBuf round;          // a round: [R float4 planes][R flags][R counts][4 words: the finite points, the inliers]
-                           // a batch: [7 S words: the pack's boxes and finite counts][E flags][E counts] ... [E planes]
-    DevBuf bins;           // the refit's limbs + the tail (p0); a batch: the scans' bins
+    DevBuf pts;            // the packed clouds, batch positions
+    DevBuf round;          // [7 S words: the boxes (a batch's pack) and finite counts][E flags][E counts] ... [E planes]
+    DevBuf bins;           // the refitted scans' bins
     DevBuf flag, pos;      // the selection's scan
     DevBuf idx, labels;    // host outputs on their way
-    DevBuf pout;           // a batch: the points of a caller in host memory on their way
-    DevBuf rows, fin, out, offs;  // a batch: the round's table, the scans' SacFin and SacOut, the offsets and inlier counts
+    DevBuf pout;           // the points of a caller in host memory on their way
+    DevBuf out;            // [S SacOut][S + 1 offsets][S inlier counts]
+    DevBuf rows, fin;      // a batch: the round's table, the scans' SacFin
     PairStage stage;       // a batch's scan table and host clouds up (wm_stage.hpp)
-    PinnedBuf h_round, h_bins;
-    PinnedBuf h_rows, h_fin, h_out;
+    PinnedBuf h_round, h_out;
+    PinnedBuf h_rows, h_fin;
 };
 
 void sac_release(wm_ctx *ctx) {
     SacWs *w = static_cast<SacWs *>(ctx->sac);
     if (!w) return;
-    DevBuf *bufs[] = {&w->pts, &w->round, &w->bins, &w->flag, &w->pos, &w->idx, &w->labels, &w->pout, &w->rows, &w->fin,
-                      &w->out, &w->offs};
+    DevBuf *bufs[] = {&w->pts, &w->round, &w->bins, &w->flag, &w->pos, &w->idx, &w->labels, &w->pout, &w->out, &w->rows,
+                      &w->fin};
     for (DevBuf *b : bufs) b->release();
     w->stage.release();
-    PinnedBuf *pins[] = {&w->h_round, &w->h_bins, &w->h_rows, &w->h_fin, &w->h_out};
+    PinnedBuf *pins[] = {&w->h_round, &w->h_out, &w->h_rows, &w->h_fin};
     for (PinnedBuf *b : pins) b->release();
     delete w;
     ctx->sac = nullptr;
@@ -493,151 +472,7 @@ unsigned sac_round_max(const wm_ctx *ctx) { return (unsigned) std::min(std::max(
 
 unsigned sac_count_blocks(size_t n) { return (unsigned) std::min<size_t>((n + kSacTile - 1) / kSacTile, kSacMaxBlocks); }
 
-// The single call's refit: the sums from its kSacBins bins (fetched), then the plane of the sums (wm_sac_walk.hpp).
-bool sac_refit(const long long *bins, const float *p0, double m, const float model[4], float out[4]) {
-    double sum[kSacComps];
-    for (int c = 0; c < kSacComps; ++c) sum[c] = sac_bins_sum(bins, kSacBins, c);
-    bool poison = false;
-    for (int b = 0; b < kSacBins; ++b) poison = poison || bins[(size_t) b * kSacBinSize + kSacPoison] != 0ll;
-    return sac_plane_from_sums(sum, poison, p0, m, model, out);
-}
-
-int sac_run(wm_ctx *ctx, const void *pts_in, size_t n, size_t stride, int mem, const wm_sac_params *p, float *coef_out,
-            int32_t *indices_out, size_t cap, int out_mem, size_t *n_out, uint8_t *labels_out, wm_sac_stats *stats) {
-    WM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->sac) ctx->sac = new SacWs();
-    SacWs &w = *static_cast<SacWs *>(ctx->sac);
-    hipStream_t st = ctx->stream;
-    const bool host_out = out_mem == WM_MEM_HOST, timed = stats != nullptr;
-    const unsigned nu = (unsigned) n;
-    const unsigned Rmax = sac_round_max(ctx);
-    const float thr = sac_threshold(p->distance_threshold);
-    const SacAxis ax = sac_axis(p);
-
-    // a round's record: the planes, the flags, the counts, four words of results
-    const size_t round_bytes = (size_t) Rmax * (sizeof(float4) + 8) + 16;
-    WM_HIP(ctx, w.pts.reserve(n * sizeof(float4)));
-    WM_HIP(ctx, w.round.reserve(round_bytes));
-    WM_HIP(ctx, w.h_round.reserve(round_bytes));
-    float4 *d_pts = w.pts.as<float4>();
-    float4 *d_planes = w.round.as<float4>();
-    unsigned *d_flags = reinterpret_cast<unsigned *>(d_planes + Rmax), *d_counts = d_flags + Rmax, *d_res = d_counts + Rmax;
-    const float4 *h_planes = w.h_round.as<float4>();
-    const unsigned *h_flags = reinterpret_cast<const unsigned *>(h_planes + Rmax), *h_counts = h_flags + Rmax,
-                   *h_res = h_counts + Rmax;
-
-    if (timed) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
-    WM_TRY(pack_cloud(ctx, pts_in, n, stride, mem, d_pts));
-    WM_HIP(ctx, hipMemsetAsync(d_res, 0, 16, st));
-    const unsigned count_blocks = sac_count_blocks(n);
-
-    // ---- PCL's loop over the stream, a round at a time (wm_sac_walk.hpp)
-    SacWalk walk;
-    walk.start(p->max_iterations, p->probability, n);
-    float model[4] = {0.f, 0.f, 0.f, 0.f};
-    size_t n_finite = 0;
-    while (walk.going) {
-        const unsigned R = walk.round_size(Rmax);
-        hipLaunchKernelGGL(k_sac_hypotheses, dim3(blocks_of(R)), dim3(kBlock), 0, st, (const float4 *) d_pts, nu,
-                           (unsigned long long) p->seed, walk.j, R, ax, d_planes, d_flags, d_counts);
-        hipLaunchKernelGGL(k_sac_count, dim3(count_blocks), dim3(kBlock), 0, st, (const float4 *) d_pts, nu,
-                           (const float4 *) d_planes, (const unsigned *) d_flags, R, thr, d_counts,
-                           walk.rounds == 0 ? d_res : (unsigned *) nullptr);
-        WM_HIP(ctx, hipGetLastError());
-        WM_TRY(fast_fetch(ctx, w.h_round.p, w.round.p, round_bytes));
-        if (walk.rounds == 0) n_finite = h_res[0];
-        walk.feed_round(h_flags, h_counts, R, [&](unsigned e) { memcpy(model, &h_planes[e], sizeof(model)); });
-    }
-    const long long best = walk.best, best_j = walk.best_j;
-    if (stats) {
-        stats->n_finite = n_finite;
-        stats->iterations = (int) walk.it;
-        stats->skipped = (int) walk.skipped;
-        stats->rounds = walk.rounds;
-        stats->hypotheses = (long long) walk.j;
-        stats->best_hypothesis = best_j;
-    }
-    auto finish_timing = [&]() {
-        if (!timed) return;
-        (void) hipEventRecord(ctx->ev_b, st);
-        (void) hipStreamSynchronize(st);
-        float ms = 0.f;
-        (void) hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b);
-        stats->kernel_ms = ms;
-    };
-    if (best_j < 0) {
-        finish_timing();
-        return WM_NOT_CONVERGED;
-    }
-    if (stats) {
-        stats->n_inliers_model = (size_t) best;
-        memcpy(stats->model_coefficients, model, sizeof(model));
-    }
-
-    // ---- the refit
-    float coef[4] = {model[0], model[1], model[2], model[3]};
-    int refined = 0;
-    if (p->optimize_coefficients && best >= 4) {
-        unsigned s[3];
-        sac_sample((unsigned long long) p->seed, (unsigned long long) best_j, nu, s);
-        const size_t bins_bytes = kSacBinWords * sizeof(long long) + sizeof(float4);
-        WM_HIP(ctx, w.bins.reserve(bins_bytes));
-        WM_HIP(ctx, w.h_bins.reserve(bins_bytes));
-        long long *d_bins = w.bins.as<long long>();
-        WM_HIP(ctx, hipMemsetAsync(d_bins, 0, bins_bytes, st));
-        hipLaunchKernelGGL(k_sac_sums, dim3(blocks_of(n)), dim3(kBlock), 0, st, (const float4 *) d_pts, nu,
-                           make_float4(model[0], model[1], model[2], model[3]), thr, s[0], d_bins,
-                           reinterpret_cast<float4 *>(d_bins + kSacBinWords));
-        WM_HIP(ctx, hipGetLastError());
-        WM_TRY(fast_fetch(ctx, w.h_bins.p, w.bins.p, bins_bytes));
-        const long long *h_bins = w.h_bins.as<long long>();
-        if (sac_refit(h_bins, reinterpret_cast<const float *>(h_bins + kSacBinWords), (double) best, model, coef)) refined = 1;
-        else memcpy(coef, model, sizeof(coef));
-    }
-
-    // ---- the selection with the returned coefficients
-    WM_HIP(ctx, w.flag.reserve(n * 4));
-    WM_HIP(ctx, w.pos.reserve((n + 1) * 4));
-    unsigned char *d_labels = labels_out;
-    if (labels_out && host_out) {
-        WM_HIP(ctx, w.labels.reserve(n));
-        d_labels = w.labels.as<unsigned char>();
-    }
-    int *d_idx = indices_out;
-    if (host_out && cap > 0) {
-        WM_HIP(ctx, w.idx.reserve(std::min(cap, n) * 4));
-        d_idx = w.idx.as<int>();
-    }
-    unsigned *flag = w.flag.as<unsigned>(), *pos = w.pos.as<unsigned>();
-    hipLaunchKernelGGL(k_sac_select, dim3(blocks_of(n)), dim3(kBlock), 0, st, (const float4 *) d_pts, nu,
-                       make_float4(coef[0], coef[1], coef[2], coef[3]), thr, flag, d_labels);
-    WM_HIP(ctx, hipGetLastError());
-    WM_TRY(exclusive_scan(ctx, flag, n, pos));
-    if (cap > 0) {
-        hipLaunchKernelGGL(k_sac_compact, dim3(blocks_of(n)), dim3(kBlock), 0, st, (const unsigned *) flag, (const unsigned *) pos,
-                           nu, (unsigned) std::min(cap, n), d_idx);
-        WM_HIP(ctx, hipGetLastError());
-    }
-    WM_TRY(fast_fetch(ctx, w.h_round.p, pos + n, 4));
-    const size_t n_in = *w.h_round.as<unsigned>();
-    finish_timing();
-    WM_HIP(ctx, hipStreamSynchronize(st));
-    const size_t n_idx = std::min(n_in, cap);
-    if (host_out) {
-        if (n_idx) WM_HIP(ctx, hipMemcpy(indices_out, d_idx, n_idx * 4, hipMemcpyDeviceToHost));
-        if (labels_out) WM_HIP(ctx, hipMemcpy(labels_out, d_labels, n, hipMemcpyDeviceToHost));
-    }
-    memcpy(coef_out, coef, sizeof(coef));
-    *n_out = n_in;
-    if (stats) {
-        stats->n_inliers = n_in;
-        stats->refined = refined;
-    }
-    return n_in > cap ? WM_ERR_ARG : WM_OK;
-}
-
-// ------------------------------------------------------------------ a batch
-// A fetch of a batch: small ones by fast_fetch's one workgroup, large ones (a long round of many scans) by the copy engine.
+// A fetch: small ones by fast_fetch's one workgroup, large ones (a long round of many scans) by the copy engine.
 int sac_fetch(wm_ctx *ctx, void *dst_pinned, const void *src_dev, size_t bytes) {
     if (bytes <= ((size_t) 64 << 10)) return fast_fetch(ctx, dst_pinned, src_dev, bytes);
     WM_HIP(ctx, hipMemcpyAsync(dst_pinned, src_dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -645,31 +480,34 @@ int sac_fetch(wm_ctx *ctx, void *dst_pinned, const void *src_dev, size_t bytes) 
     return WM_OK;
 }
 
-struct SacBatchCall {
+// A call of either entry point: wm_sac_segment_batch's arguments, which wm_sac_segment fills for its one scan.
+struct SacCall {
+    bool single;  // wm_sac_segment: the scan by value, no table; no labels without a model; timed only with stats
     const wm_sac_scan *scans;
     unsigned S;
     size_t stride;
     int mem;
     const wm_sac_params *p;
     int negative;
-    float *coefficients_out;
+    float *coefficients_out;  // 4 S
     int32_t *indices_out;
     size_t cap;
     void *points_out;
     size_t out_stride;
     bool host_out;
-    size_t *offsets_out;
+    size_t *offsets_out;  // S + 1
     uint8_t *labels_out;
-    int *status;
+    int *status;          // S, WM_NOT_CONVERGED on entry
     wm_sac_stats *stats;
     float *kernel_ms;
 };
 
-// The batch (arguments checked, the outputs' defaults written, at least one scan of n >= 3).  Launches and host waits:
-// the front (upload, pack), per round of the longest-living scan the round's table up, two launches and one fetch, then
-// the models (and the refit's sums) with one fetch, the coefficients up, select / scan / compact and one fetch of the
-// offsets -- whatever the number of scans.
-int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
+// Either entry point (arguments checked, the outputs' defaults written, at least one scan of n >= 3).  Launches and
+// host waits: the front (a batch: upload; pack), per round of the longest-living scan two launches and one fetch (a
+// batch: the round's table up), then the models and, where a scan is refitted, the sums with one fetch of their own (a
+// batch: the coefficients up), select / scan / compact and one fetch of the offsets -- whatever the number of scans.
+// The single call uploads nothing and waits once per round, once for the refit and once at the end.
+int sac_call(wm_ctx *ctx, const SacCall &c) {
     WM_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->sac) ctx->sac = new SacWs();
     SacWs &w = *static_cast<SacWs *>(ctx->sac);
@@ -680,9 +518,10 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
     const float thr = sac_threshold(p->distance_threshold);
     const SacAxis ax = sac_axis(p);
     const unsigned long long seed = (unsigned long long) p->seed;
+    const bool timed = !c.single || c.stats;  // (a batch's PairStage::submit records ev_a)
 
-    // ---- the front.  A scan of n < 3 has no sample: it gets no batch position and no workgroup (n = 0 in the table);
-    // aux0 is a scan's first label, which counts such a scan's points
+    // ---- the scans' walks and the sizes of the first round.  A scan of n < 3 has no sample: it gets no batch position
+    // and no workgroup (n = 0 in the table)
     std::vector<wm_sac_scan> rows_in(c.scans, c.scans + S);
     std::vector<SacWalk> walk(S);
     std::vector<unsigned> live;
@@ -702,18 +541,31 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
     // the round's words: [6 S boxes][S finite counts][E flags][E counts], the planes behind them at a fixed place
     const size_t planes_at = (7 * (size_t) S + 2 * E0 + 3) & ~(size_t) 3;  // (words; a float4's alignment)
     const size_t round_bytes = planes_at * 4 + E0 * sizeof(float4);
-    WM_HIP(ctx, w.h_round.reserve(std::max((size_t) S + 2 * E0, 2 * (size_t) S + 1) * 4));  // (a round; the offsets' fetch)
-    WM_HIP(ctx, w.rows.reserve((live.size() + 1) * sizeof(SacRow)));
+    const size_t out_bytes = (size_t) S * sizeof(SacOut);  // (behind the SacOuts: S + 1 offsets, S inlier counts)
+    WM_HIP(ctx, w.h_round.reserve(((size_t) S + 2 * E0) * 4));
     WM_HIP(ctx, w.h_rows.reserve((live.size() + 1) * sizeof(SacRow)));
-    WM_HIP(ctx, w.fin.reserve((size_t) S * sizeof(SacFin)));
     WM_HIP(ctx, w.h_fin.reserve((size_t) S * sizeof(SacFin)));
-    WM_HIP(ctx, w.out.reserve((size_t) S * sizeof(SacOut)));
-    WM_HIP(ctx, w.h_out.reserve((size_t) S * sizeof(SacOut)));
-    WM_HIP(ctx, w.offs.reserve((2 * (size_t) S + 1) * 4));
+    WM_HIP(ctx, w.out.reserve(out_bytes + (2 * (size_t) S + 1) * 4));
+    WM_HIP(ctx, w.h_out.reserve(out_bytes + (2 * (size_t) S + 1) * 4));
+    // ---- the front: the packed points, the scan table (aux0 is a scan's first label, which counts a tiny scan's points)
     ScanTable T;
-    WM_TRY(scan_table_pack(ctx, w.stage, rows_in.data(), S, c.stride, c.mem, w.pts, w.round, round_bytes, &T));
-    const size_t total = T.total;
-    {  // the labels' places; the table goes up again with them (the pack did not read them)
+    ClScan one{};
+    if (c.single) {  // no table on the device: the one scan owns position 0, workgroup 0 and label 0 of everything
+        WM_HIP(ctx, w.pts.reserve(c.scans[0].n * sizeof(float4)));
+        WM_HIP(ctx, w.round.reserve(round_bytes));
+        if (timed) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
+        WM_TRY(pack_cloud(ctx, c.scans[0].pts, c.scans[0].n, c.stride, c.mem, w.pts.as<float4>()));
+        WM_HIP(ctx, hipMemsetAsync(w.round.as<unsigned>() + 6, 0, 4, st));  // (the finite points: the first round's count)
+        one.n = (unsigned) c.scans[0].n;
+        T.tab = &one;
+        T.S = 1;
+        T.total = one.n;
+        T.blocks = blocks_of(one.n);
+    } else {
+        WM_HIP(ctx, w.rows.reserve((live.size() + 1) * sizeof(SacRow)));
+        WM_HIP(ctx, w.fin.reserve((size_t) S * sizeof(SacFin)));
+        WM_TRY(scan_table_pack(ctx, w.stage, rows_in.data(), S, c.stride, c.mem, w.pts, w.round, round_bytes, &T));
+        // the labels' places; the table goes up again with them (the pack did not read them)
         size_t at = 0;
         for (unsigned k = 0; k < S; ++k) {
             T.tab[k].aux0 = (unsigned) at;
@@ -721,6 +573,7 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
         }
         WM_HIP(ctx, hipMemcpyAsync(w.stage.up.dev.p, w.stage.up.host.p, T.table_bytes, hipMemcpyHostToDevice, st));
     }
+    const size_t total = T.total;
     const float4 *d_pts = w.pts.as<float4>();
     unsigned *d_words = w.round.as<unsigned>();
     float4 *d_planes = reinterpret_cast<float4 *>(d_words + planes_at);
@@ -748,11 +601,16 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
         }
         h_rows[L] = SacRow{0ull, S, 0u, E, cb, 0u, 0u, 0u, 0u};
         unsigned *d_flags = d_words + 7 * (size_t) S, *d_counts = d_flags + E;
-        WM_HIP(ctx, hipMemcpyAsync(w.rows.p, h_rows, ((size_t) L + 1) * sizeof(SacRow), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_sac_hypotheses_batch, dim3(blocks_of(E)), dim3(kBlock), 0, st, d_pts,
-                           (const SacRow *) w.rows.as<SacRow>(), L, E, seed, ax, d_planes, d_flags, d_counts);
-        hipLaunchKernelGGL(k_sac_count_batch, dim3(cb), dim3(kBlock), 0, st, d_pts, (const SacRow *) w.rows.as<SacRow>(), L,
-                           (const float4 *) d_planes, (const unsigned *) d_flags, thr, d_counts);
+        SacRows rows{nullptr, L, h_rows[0]};
+        if (!c.single) {
+            WM_HIP(ctx, hipMemcpyAsync(w.rows.p, h_rows, ((size_t) L + 1) * sizeof(SacRow), hipMemcpyHostToDevice, st));
+            rows.tab = w.rows.as<SacRow>();
+        }
+        hipLaunchKernelGGL(k_sac_hypotheses, dim3(blocks_of(E)), dim3(kBlock), 0, st, d_pts, rows, E, seed, ax, d_planes, d_flags,
+                           d_counts);
+        hipLaunchKernelGGL(k_sac_count, dim3(cb), dim3(kBlock), 0, st, d_pts, rows, (const float4 *) d_planes,
+                           (const unsigned *) d_flags, thr, d_counts,
+                           c.single && round == 0 ? d_words + 6 : (unsigned *) nullptr);
         WM_HIP(ctx, hipGetLastError());
         // the round's (flag, count) pairs of the live scans; in front of the first round's the pack's finite counts
         const unsigned *h_flags = h_words + S;
@@ -808,61 +666,69 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
         WM_HIP(ctx, w.labels.reserve(label_total));
         d_labels = w.labels.as<unsigned char>();
     }
-    auto finish = [&](float *ms) -> int {  // (the stream has been waited for; ev_b lies behind the last launch)
-        if (hipEventElapsedTime(ms, ctx->ev_a, ctx->ev_b) != hipSuccess) *ms = 0.f;
-        if (c.kernel_ms) *c.kernel_ms = *ms;
+    auto finish = [&]() -> int {  // (the stream has been waited for)
+        float ms = 0.f;
+        if (timed && hipEventElapsedTime(&ms, ctx->ev_a, ctx->ev_b) != hipSuccess) ms = 0.f;
+        if (c.kernel_ms) *c.kernel_ms = ms;
         if (c.stats)
             for (unsigned k = 0; k < S; ++k)
-                if (c.scans[k].n >= 3) c.stats[k].kernel_ms = *ms;
-        if (c.host_out && c.labels_out) WM_HIP(ctx, hipMemcpy(c.labels_out, d_labels, label_total, hipMemcpyDeviceToHost));
+                if (c.scans[k].n >= 3) c.stats[k].kernel_ms = ms;
+        if (c.host_out && d_labels) WM_HIP(ctx, hipMemcpy(c.labels_out, d_labels, label_total, hipMemcpyDeviceToHost));
         return WM_OK;
     };
-    float ms = 0.f;
-    if (!any_model) {  // every slice is empty and every label NONE
+    if (!any_model) {  // every slice is empty; a batch's labels are NONE, the single call writes none
+        if (c.single) d_labels = nullptr;
         if (d_labels) WM_HIP(ctx, hipMemsetAsync(d_labels, 0, label_total, st));
-        WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+        if (timed) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
         WM_HIP(ctx, hipStreamSynchronize(st));
-        return finish(&ms);
+        return finish();
     }
 
-    // ---- the models again from their entries, the refit's sums in the single call's bins and order; one fetch
-    const ClScan *d_tab = T.d_tab;
-    const SacFin *d_fin = w.fin.as<SacFin>();
+    // ---- the models again from their entries; where a scan is refitted, its sums and one fetch of the SacOuts
+    SacScans sc{T.d_tab, w.fin.as<SacFin>(), S, one, h_fin[0]};
     SacOut *d_out = w.out.as<SacOut>();
-    WM_HIP(ctx, hipMemcpyAsync(w.fin.p, h_fin, (size_t) S * sizeof(SacFin), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sac_models, dim3(blocks_of(S)), dim3(kBlock), 0, st, d_tab, d_fin, S, d_pts, seed, ax, d_out);
+    const SacOut *h_out = w.h_out.as<SacOut>();
+    if (sc.tab) WM_HIP(ctx, hipMemcpyAsync(w.fin.p, h_fin, (size_t) S * sizeof(SacFin), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sac_models, dim3(blocks_of(S)), dim3(kBlock), 0, st, sc, d_pts, seed, ax, d_out);
     if (n_bins) {
         WM_HIP(ctx, w.bins.reserve(n_bins * kSacBinSize * sizeof(long long)));
         long long *d_bins = w.bins.as<long long>();
         WM_HIP(ctx, hipMemsetAsync(d_bins, 0, n_bins * kSacBinSize * sizeof(long long), st));
-        hipLaunchKernelGGL(k_sac_sums_batch, dim3((unsigned) T.blocks), dim3(kBlock), 0, st, d_tab, S, d_fin,
-                           (const SacOut *) d_out, d_pts, thr, d_bins);
-        hipLaunchKernelGGL(k_sac_bins_sums, dim3(S), dim3(64), 0, st, d_fin, (const long long *) d_bins, d_out);
+        hipLaunchKernelGGL(k_sac_sums, dim3((unsigned) T.blocks), dim3(kBlock), 0, st, sc, (const SacOut *) d_out, d_pts, thr,
+                           d_bins);
+        hipLaunchKernelGGL(k_sac_bins_sums, dim3(S), dim3(kSacBins), 0, st, sc, (const long long *) d_bins, d_out);
     }
     WM_HIP(ctx, hipGetLastError());
-    WM_TRY(sac_fetch(ctx, w.h_out.p, d_out, (size_t) S * sizeof(SacOut)));
-    const SacOut *h_out = w.h_out.as<SacOut>();
-    std::vector<int> refined(S, 0);
-    for (unsigned k = 0; k < S; ++k) {
-        SacFin &f = h_fin[k];
-        if (f.best_j < 0) continue;
-        const SacOut &o = h_out[k];
-        const float model[4] = {o.model.x, o.model.y, o.model.z, o.model.w};
-        const float p0[3] = {o.p0.x, o.p0.y, o.p0.z};
-        float coef[4] = {model[0], model[1], model[2], model[3]};
-        if (f.refit) {
-            if (sac_plane_from_sums(o.sum, o.poison != 0u, p0, (double) walk[k].best, model, coef)) refined[k] = 1;
-            else memcpy(coef, model, sizeof(coef));
+    // the SacOuts at home: the scans' returned planes (the refit on the host, wm_sac_walk.hpp) and what the caller gets
+    auto planes_home = [&]() {
+        for (unsigned k = 0; k < S; ++k) {
+            SacFin &f = h_fin[k];
+            if (f.best_j < 0) continue;
+            const SacOut &o = h_out[k];
+            const float model[4] = {o.model.x, o.model.y, o.model.z, o.model.w};
+            const float p0[3] = {o.p0.x, o.p0.y, o.p0.z};
+            float coef[4] = {model[0], model[1], model[2], model[3]};
+            int refined = 0;
+            if (f.refit) {
+                if (sac_plane_from_sums(o.sum, o.poison != 0u, p0, (double) walk[k].best, model, coef)) refined = 1;
+                else memcpy(coef, model, sizeof(coef));
+            }
+            f.has = 1u;
+            f.coef = make_float4(coef[0], coef[1], coef[2], coef[3]);
+            memcpy(c.coefficients_out + 4 * (size_t) k, coef, sizeof(coef));
+            c.status[k] = WM_OK;
+            if (c.stats) {
+                c.stats[k].n_inliers_model = (size_t) walk[k].best;
+                memcpy(c.stats[k].model_coefficients, model, sizeof(model));
+                c.stats[k].refined = refined;
+            }
         }
-        f.has = 1u;
-        f.coef = make_float4(coef[0], coef[1], coef[2], coef[3]);
-        memcpy(c.coefficients_out + 4 * (size_t) k, coef, sizeof(coef));
-        c.status[k] = WM_OK;
-        if (c.stats) {
-            c.stats[k].n_inliers_model = (size_t) walk[k].best;
-            memcpy(c.stats[k].model_coefficients, model, sizeof(model));
-            c.stats[k].refined = refined[k];
-        }
+    };
+    if (n_bins) {  // the selection takes the planes from the SacFins; else it reads the models where k_sac_models left them
+        WM_TRY(sac_fetch(ctx, w.h_out.p, d_out, out_bytes));
+        planes_home();
+        sc.fin1 = h_fin[0];
+        if (sc.tab) WM_HIP(ctx, hipMemcpyAsync(w.fin.p, h_fin, (size_t) S * sizeof(SacFin), hipMemcpyHostToDevice, st));
     }
 
     // ---- the selection with the returned coefficients, over the batch
@@ -880,29 +746,33 @@ int sac_batch(wm_ctx *ctx, const SacBatchCall &c) {
         }
     }
     unsigned *flag = w.flag.as<unsigned>(), *pos = w.pos.as<unsigned>();
-    unsigned *d_offs = w.offs.as<unsigned>(), *d_ninl = d_offs + S + 1;
-    WM_HIP(ctx, hipMemcpyAsync(w.fin.p, h_fin, (size_t) S * sizeof(SacFin), hipMemcpyHostToDevice, st));
+    unsigned *d_offs = reinterpret_cast<unsigned *>(d_out + S), *d_ninl = d_offs + S + 1;
     if (c.negative) WM_HIP(ctx, hipMemsetAsync(d_ninl, 0, (size_t) S * 4, st));
     if (d_labels && tiny) WM_HIP(ctx, hipMemsetAsync(d_labels, 0, label_total, st));  // (no workgroup writes a tiny scan's)
-    hipLaunchKernelGGL(k_sac_select_batch, dim3((unsigned) T.blocks), dim3(kBlock), 0, st, d_tab, S, d_fin, d_pts, thr,
+    hipLaunchKernelGGL(k_sac_select, dim3((unsigned) T.blocks), dim3(kBlock), 0, st, sc, (const SacOut *) d_out, d_pts, thr,
                        c.negative, flag, d_labels, c.negative ? d_ninl : (unsigned *) nullptr);
     WM_HIP(ctx, hipGetLastError());
     WM_TRY(exclusive_scan(ctx, flag, total, pos));
-    hipLaunchKernelGGL(k_sac_compact_batch, dim3(std::max((unsigned) T.blocks, blocks_of((size_t) S + 1))), dim3(kBlock), 0, st,
-                       d_tab, S, (unsigned) T.blocks, (unsigned) total, d_pts, (const unsigned *) flag, (const unsigned *) pos,
-                       d_idx, d_cap, d_pout, c.out_stride, d_offs);
+    hipLaunchKernelGGL(k_sac_compact, dim3(std::max((unsigned) T.blocks, blocks_of((size_t) S + 1))), dim3(kBlock), 0, st, sc,
+                       (unsigned) T.blocks, (unsigned) total, d_pts, (const unsigned *) flag, (const unsigned *) pos, d_idx, d_cap,
+                       d_pout, c.out_stride, d_offs);
     WM_HIP(ctx, hipGetLastError());
-    WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
-    const size_t offs_words = (size_t) S + 1 + (c.negative ? S : 0);
-    WM_TRY(sac_fetch(ctx, w.h_round.p, d_offs, offs_words * 4));
+    // kernel_ms ends behind a batch's last launch and behind the single call's last fetch.  That fetch: the offsets (and
+    // the inlier counts), behind the SacOuts where these have not come home yet
+    if (timed && !c.single) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
+    const size_t from = n_bins ? out_bytes : 0, offs_words = (size_t) S + 1 + (c.negative ? S : 0);
+    WM_TRY(sac_fetch(ctx, w.h_out.as<unsigned char>() + from, w.out.as<unsigned char>() + from,
+                     out_bytes - from + offs_words * 4));
+    if (timed && c.single) WM_HIP(ctx, hipEventRecord(ctx->ev_b, st));
     WM_HIP(ctx, hipStreamSynchronize(st));
-    const unsigned *h_offs = w.h_round.as<unsigned>(), *h_ninl = h_offs + S + 1;
+    if (!n_bins) planes_home();
+    const unsigned *h_offs = reinterpret_cast<const unsigned *>(h_out + S), *h_ninl = h_offs + S + 1;
     for (unsigned k = 0; k <= S; ++k) c.offsets_out[k] = h_offs[k];
     const size_t kept = h_offs[S];
     if (c.stats)
         for (unsigned k = 0; k < S; ++k)
-            if (h_fin[k].has) c.stats[k].n_inliers = c.negative ? h_ninl[k] : h_offs[k + 1] - h_offs[k];
-    WM_TRY(finish(&ms));
+            if (h_fin[k].best_j >= 0) c.stats[k].n_inliers = c.negative ? h_ninl[k] : h_offs[k + 1] - h_offs[k];
+    WM_TRY(finish());
     const size_t m = std::min(kept, c.cap);
     if (c.host_out) {
         if (m) WM_HIP(ctx, hipMemcpy(c.indices_out, d_idx, m * 4, hipMemcpyDeviceToHost));
@@ -942,7 +812,14 @@ int wm_sac_segment(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int me
         stats->best_hypothesis = -1;
     }
     if (n < 3) return WM_NOT_CONVERGED;  // (no sample: no device is touched)
-    return sac_run(ctx, pts, n, stride, mem, p, coefficients_out, indices_out, cap, out_mem, n_out, labels_out, stats);
+    const wm_sac_scan scan{pts, n};
+    size_t offs[2] = {0, 0};
+    int status = WM_NOT_CONVERGED;
+    const SacCall c{true, &scan, 1, stride, mem, p, 0, coefficients_out, indices_out, cap, nullptr, 0, out_mem == WM_MEM_HOST,
+                    offs, labels_out, &status, stats, nullptr};
+    const int rc = sac_call(ctx, c);
+    *n_out = offs[1];
+    return rc == WM_OK ? status : rc;
 }
 
 int wm_sac_segment_batch(wm_ctx *ctx, const wm_sac_scan *scans, int n_scans, size_t stride, int mem, const wm_sac_params *p,
@@ -974,9 +851,9 @@ int wm_sac_segment_batch(wm_ctx *ctx, const wm_sac_scan *scans, int n_scans, siz
         if (labels_out && out_mem == WM_MEM_HOST && total) memset(labels_out, 0, total);
         return WM_OK;
     }
-    const SacBatchCall c{scans, S, stride, mem, p, negative, coefficients_out, indices_out, cap, points_out,
-                         points_out ? out_stride : 0, out_mem == WM_MEM_HOST, offsets_out, labels_out, status, stats, kernel_ms};
-    return sac_batch(ctx, c);
+    const SacCall c{false, scans, S, stride, mem, p, negative, coefficients_out, indices_out, cap, points_out,
+                    points_out ? out_stride : 0, out_mem == WM_MEM_HOST, offsets_out, labels_out, status, stats, kernel_ms};
+    return sac_call(ctx, c);
 }
 
 }  // extern "C"

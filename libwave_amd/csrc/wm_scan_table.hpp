@@ -4,7 +4,8 @@
 // wm_outlier_filter_batch); wm_sac_segment_batch needs no lattice and stops here.
 //
 // Included by the units that run a batch (each gets kernels of its own: the names are the cluster extraction's, where
-// they were written).
+// they were written).  Their single calls run the same kernels without a table: tab == nullptr and one ClScan by value
+// (OlScans in wm_outlier.hip, SacScans in wm_sac.hip), which cl_find's look-up in a table of one never reads.
 #pragma once
 #include <string.h>
 
