@@ -704,10 +704,12 @@ int ensure_levels(wm_ctx *ctx, double max_corr) {
     (void) pts;
     ctx->n_levels = L;
     ctx->levels_max_corr = max_corr;
-    // publish the ladder for the search kernel
+    // publish the ladder for the search kernels: every launch takes it by value, as a kernel argument (levels_dev),
+    // and looks a level chosen at run time up in the copy in device memory
     LevelsDev host{};
     for (int l = 0; l < L; ++l) host.g[l] = ctx->levels[l].d;
     host.n = L;
+    ctx->levels_dev = host;
     WM_HIP(ctx, ctx->d_levels.reserve(sizeof(LevelsDev)));
     // staged in pinned memory the ctx owns: the copy is asynchronous and needs no wait (the
     // next user of the scratch waits on the stream before touching it)

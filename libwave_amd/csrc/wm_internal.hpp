@@ -171,7 +171,9 @@ struct GridDev {
     const uint32_t *cell_start; // nx*ny*nz + 1
 };
 
-struct LevelsDev {  // the level ladder as the search kernel reads it (lives in HBM)
+// the level ladder as the search kernels read it: a kernel argument BY VALUE (340 bytes of the kernarg segment: depth, cell
+// sizes and level 0 are there when the wave starts) and a copy in HBM for the look-up of a level chosen at run time
+struct LevelsDev {
     GridDev g[kMaxLevels];
     int n;
 };
@@ -187,18 +189,29 @@ struct GridLevel {
 // Lives in device memory so that a whole registration runs without the host
 // in the loop; mirrored to pinned host memory when the host needs to look.
 struct IcpDevState {
-    double T[16];   // cumulative source->target
+    // ---- what a search wave reads before it can start (k_nn_grid, k_nn_cert): ONE aligned run of 80 bytes at the head
+    // of the struct, fetched by two wide scalar loads issued together (nn_state, wm_nn_scan.hpp) -- these words used to
+    // sit up to 0x4b4 bytes apart, a scalar round trip each where the compiler did not merge them
     float Tf[12];   // float rows 0..2 of T (what the correspondence kernel applies)
-    float Tf_search[12];  // ... the last correspondence search ran under (set by the solve that consumed it): what the keys' d2 refer to
-    double Tk[16];  // last incremental step
-    double stats[kStatsLen];
-    double mse, prev_mse;
-    int iter, done, converged, state, n_corr, max_iter, forced, mode;
+    int done;
     int have_prev;  // keys[] hold the previous iteration's result (level prediction)
     // sharded registration: this rank handles the source points whose transformed x
     // lies in [slab_lo, slab_hi)
     int slab_on;
     float slab_lo, slab_hi;
+    // the count of changed matches rides in the fraction of the handled-points sum (units of 2^-24, wm_nn_scan.hpp:
+    // icp_terms); beyond 2^23 queries per context only every (changed_mask + 1)-th query is counted, so
+    // that the fraction can never carry into the integer part, and the count is scaled back up here
+    unsigned changed_mask;
+    float step_disp;   // upper estimate of how far the last step moved the source points (metres)
+    int iter;  // (not read by the searches: it fills the run to a multiple of 8 bytes)
+    // ---- the rest, in no particular order
+    double T[16];   // cumulative source->target
+    float Tf_search[12];  // ... the last correspondence search ran under (set by the solve that consumed it): what the keys' d2 refer to
+    double Tk[16];  // last incremental step
+    double stats[kStatsLen];
+    double mse, prev_mse;
+    int converged, state, n_corr, max_iter, forced, mode;
     // every rank holds only the source points near its slab; the all-reduced count of
     // handled points must equal the cloud size in EVERY iteration, else a point fell
     // outside all bands and the registration has to be redone with full source clouds
@@ -216,13 +229,8 @@ struct IcpDevState {
     double local_handled;  // queries THIS rank handled in the last search (sharded: before the all-reduce)
     float frac_changed;    // fraction of the handled queries whose match changed in the last search
     float frac_unsettled;  // fraction the last certificate launch had to search (0 after a full search)
-    float step_disp;   // upper estimate of how far the last step moved the source points (metres)
     float src_radius;  // half diagonal of the source cloud's bounding box (for step_disp)
     float src_centre[3];
-    // the count of changed matches rides in the fraction of the handled-points sum (units of 2^-24, wm_nn_scan.hpp:
-    // icp_terms); beyond 2^23 queries per context only every (changed_mask + 1)-th query is counted, so
-    // that the fraction can never carry into the integer part, and the count is scaled back up here
-    unsigned changed_mask;
     int uns_global;  // sharded: the count of searched queries came through the all-reduced block (all ranks steer alike)
     int xchg_failed;  // sharded, in-kernel exchange (wm_xchg.hpp): a peer's block never arrived; the registration ended there
     // correspondence rejection (wm_reject.hip): the last executed iteration's matched count and threshold bits, copied
@@ -230,6 +238,12 @@ struct IcpDevState {
     int n_matched, reject_bits;
     int pad_;
 };
+constexpr unsigned kNnStateWords = 20;  // the head run, in 32-bit words
+static_assert(offsetof(IcpDevState, Tf) == 0 && offsetof(IcpDevState, done) == 48 && offsetof(IcpDevState, have_prev) == 52 &&
+                  offsetof(IcpDevState, slab_on) == 56 && offsetof(IcpDevState, slab_lo) == 60 &&
+                  offsetof(IcpDevState, slab_hi) == 64 && offsetof(IcpDevState, changed_mask) == 68 &&
+                  offsetof(IcpDevState, step_disp) == 72 && offsetof(IcpDevState, T) == 4 * kNnStateWords,
+              "the search kernels' head run of the state (nn_state, wm_nn_scan.hpp)");
 
 struct Bbox {
     float lo[3], hi[3];
@@ -337,6 +351,7 @@ struct wm_ctx {
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
     wm::DevBuf keys, partials, partials2, corr_tmp_idx, corr_tmp_d2, d_levels;
+    wm::LevelsDev levels_dev{};  // the ladder as ensure_levels last published it (= d_levels): what a search launch passes by value
     // the iteration's sums as exact integer limbs (wm_bins.hpp): all zero between iterations (the solve puts the
     // zeros back)
     wm::DevBuf bins;

@@ -44,28 +44,46 @@ namespace wm {
 // otherwise every lane walks its own (kept for targets of 2^26 points and more, and for comparison).
 template <int STATS, bool BAL, bool COST = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
-    k_nn_grid(const LevelsDev *__restrict__ lv, const float4 *__restrict__ src, unsigned n,
+    k_nn_grid(const LevelsDev lv, const float4 *__restrict__ src, unsigned n,
               IcpDevState *__restrict__ st, float thr_d2, unsigned long long *__restrict__ keys,
               float4 *__restrict__ match_pt, const float4 *__restrict__ tgt_orig,
               float r_light_cells, float lane_lf, float coop_lf, float r0_cells, unsigned chunk_sz,
               double *__restrict__ partials, unsigned *__restrict__ cost_out,
-              unsigned long long *__restrict__ phase_out, long long *__restrict__ bins) {
+              unsigned long long *__restrict__ phase_out, long long *__restrict__ bins, float rmax) {
     // (bins != nullptr: the wave's sums are ADDED into the iteration's bins -- exact integer limbs, any order:
     // wm_bins.hpp -- instead of being stored as a row of `partials` for k_reduce_rows to add up)
-    // (the wave's life is a chain of memory round trips; the three streams of its chunk -- source
-    // point, previous key, previous match -- need nothing but the block number for their addresses
-    // and are requested before the state is looked at.  Before the first search keys / match_pt hold
-    // nothing meaningful and are not looked at.)
+    // (the wave's life is a chain of memory round trips, and its start is TWO of them: the kernel arguments -- the
+    // level ladder among them, by value -- and then, requested together, the head run of the state (nn_state) and the
+    // three streams of its chunk: source point, previous key, previous match, whose addresses need nothing but the
+    // block number.  The first wait is at the pin below; `done` is tested behind it: a launch queued behind a `done`
+    // has loaded (from clamped indices) and leaves without storing or adding anything.  Before the first search keys /
+    // match_pt hold nothing meaningful: loaded, not looked at.  Up to eb9ee33 the compiler had the `done` test in
+    // front and the loads sunk behind it: seven dependent trips, two of them vector trips in series.)
+    // (rmax: the search radius that covers the gate, sqrt(thr_d2) with its cushion -- wave-uniform, formed on the host)
     // (chunk_sz: the XCDs take turns in chunks of this many workgroups, 0: one eighth of the queries each)
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned row = chunk_sz ? xcd_remap_chunked(blockIdx.x, chunk_sz) : xcd_remap(blockIdx.x, gridDim.x);
+    // (both remaps are formed and one is chosen: a branch on chunk_sz here would put a wait for that one argument in
+    // front of the loads of all the others)
+    const unsigned row_c = xcd_remap_chunked(blockIdx.x, max(chunk_sz, 1u)), row_e = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned row = chunk_sz ? row_c : row_e;
     const unsigned i = row * 64u + lane;
     const bool active = i < n;
     const unsigned ic = min(i, n - 1u);
     const float4 p_e = src[ic];
     const unsigned long long prev_e = keys[ic];
     const float4 tp_e = match_pt[ic];
-    if (st->done) return;
+    const NnState S = nn_state(st);
+    // the levels' cell sizes (wave-uniform); all six come from the kernel arguments at fixed offsets -- no
+    // address that depends on the depth; the unused ones (0: the host leaves them so) are never looked at (nn_level_for)
+    const int L = lv.n;
+    float hl[kMaxLevels];
+#pragma unroll
+    for (int k = 0; k < kMaxLevels; ++k) hl[k] = lv.g[k].h;
+    asm volatile("" ::WM_NN_STATE_OPERANDS(S), "v"(p_e.x), "v"(p_e.y), "v"(p_e.z), "v"(prev_e), "v"(tp_e.x), "v"(tp_e.y),
+                 "v"(tp_e.z), "v"(tp_e.w));
+    asm volatile("" ::"s"(L), "s"(hl[0]), "s"(hl[1]), "s"(hl[2]), "s"(hl[3]), "s"(hl[4]), "s"(hl[5]), "s"(r_light_cells),
+                 "s"(lane_lf), "s"(r0_cells), "s"(thr_d2), "s"(rmax));
+    if (S.done) return;
     unsigned cost = 0;
     // developer (COST): shader-clock cycles of this wave's phases, added into phase_out[8] by lane 0:
     // [0] walk, [1] rounds, [2] walks, [3] prologue, [4] pass loop, [5] cooperative phase + stores,
@@ -75,15 +93,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
     // per wave: [run][lane] = each lane's pending runs (lane scan), or the pooled trip list (balanced walk)
     __shared__ uint2 s_runs[BAL ? 1 : kRowChunk * 64];
     __shared__ BalHolder<BAL> s_hold;
-    const int L = lv->n;
     const int L_levels = L;
-    float hl[kMaxLevels];  // the levels' cell sizes (wave-uniform)
-#pragma unroll
-    for (int k = 0; k < kMaxLevels; ++k) hl[k] = lv->g[k < L ? k : 0].h;
     const float h0 = hl[0];
-    const float rmax = sqrtf(thr_d2) * 1.0001f + 1e-6f;
     const float r_light = r_light_cells * h0;  // larger radii go to the cooperative path
-    const bool have_prev = st->have_prev != 0;  // wave-uniform
+    const bool have_prev = S.have_prev != 0;  // wave-uniform
     float qx = 0.f, qy = 0.f, qz = 0.f, r = 0.f;
     float bqx = 0.f, bqy = 0.f, bqz = 0.f;  // coordinates of the previous iteration's match
     unsigned long long best = make_key(thr_d2, kNoIdx);
@@ -97,9 +110,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
             prev = prev_e;
             tp = tp_e;
         }
-        xform(st->Tf, p_e, qx, qy, qz);
+        xform(S.Tf, p_e, qx, qy, qz);
         // sharded registration: only the rank owning this x-slab handles the point
-        if (st->slab_on && !(qx >= st->slab_lo && qx < st->slab_hi)) mine = false;
+        if (S.slab_on && !(qx >= S.slab_lo && qx < S.slab_hi)) mine = false;
     }
     // a point of another rank's slab is left untouched: its key / match keep whatever this
     // rank last found for it (still a valid candidate if it ever comes back)
@@ -118,7 +131,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
                     bqx = tp.x;
                     bqy = tp.y;
                     bqz = tp.z;
-                    r = fmaxf(sqrtf(d2b) * 1.0001f + 1e-6f, 0.05f * h0);
+                    // (v_sqrt_f32, 1 ulp: the cushion of 1e-4 relative + 1e-6 m covers it; the radius steers the
+                    // scan, the certificate compares exact d2)
+                    r = fmaxf(__builtin_amdgcn_sqrtf(d2b) * 1.0001f + 1e-6f, 0.05f * h0);
                 }
             }
         }
@@ -149,10 +164,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
             const int l0 = __builtin_amdgcn_readlane(l, __ffsll((long long) lv_mask) - 1);
             float margin;
             if (__ballot(live && l != l0) == 0ull) {
-                const GridDev g = lv->g[l0];
+                const GridDev g = lv.g[l0];
                 best = scan_box_bal<COST, kBalRowChunk>(g, live, qx, qy, qz, r, best, &margin, L, lane, allow_layered, g.pts, cost, prof);
             } else {
-                const GridDev g = lv->g[l];
+                const GridDev g = lv.g[l];
                 L.base[lane] = (unsigned long long) g.pts;
                 best = scan_box_bal<COST, kBalRowChunk>(g, live, qx, qy, qz, r, best, &margin, L, lane, allow_layered, nullptr, cost, prof);
             }
@@ -170,9 +185,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
         }
     } else if (mine) {
         for (int pass = 0; !heavy && pass < 32; ++pass) {
-            int l = 0;
-            while (l < L - 1 && lv->g[l].h < lane_lf * r) ++l;
-            const GridDev g = lv->g[l];
+            const int l = nn_level_for(hl, L_levels, lane_lf, r);
+            const GridDev g = lv.g[l];
             float margin;
             best = scan_box<COST>(g, qx, qy, qz, r, best, &margin, s_runs, lane, have_prev, cost);
             if constexpr (COST) cost += 1u << 24;  // passes
@@ -198,9 +212,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
                                 rl_u((unsigned) best, sl);
         if ((unsigned) ub == kNoIdx && seed > ur) ur = fminf(seed, rmax);  // neighbour's radius
         for (int pass = 0; pass < 64; ++pass) {
-            int l = 0;
-            while (l < L - 1 && lv->g[l].h < coop_lf * ur) ++l;
-            const GridDev g = lv->g[l];
+            const int l = nn_level_for(hl, L_levels, coop_lf, ur);
+            const GridDev g = lv.g[l];
             float margin;
             ub = coop_scan_box(g, ux, uy, uz, ur, ub, lane, &margin);
             const float bd2 = __uint_as_float((unsigned) (ub >> 32));
@@ -356,12 +369,13 @@ int nn_sums_target(wm_ctx *ctx, int stats_mode, bool use_bins, unsigned blocks, 
 template <int STATS, bool BAL, bool COST = false>
 static void launch_nn_grid_t(wm_ctx *ctx, unsigned blocks, float thr_d2, unsigned xcd_chunk, long long *bins = nullptr) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_grid<STATS, BAL, COST>), dim3(blocks), dim3(64), 0, ctx->stream,
-                       ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
+                       ctx->levels_dev, ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
                        ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),
                        ctx->match_pt.as<float4>(), ctx->tgt_orig.as<float4>(), ctx->tune_r_light,
                        ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0, xcd_chunk, ctx->partials.as<double>(),
                        ctx->cost_log.p ? ctx->cost_log.as<unsigned>() + (size_t) ctx->cost_log_iter * ctx->n_src : nullptr,
-                       ctx->phase_log.p ? ctx->phase_log.as<unsigned long long>() + 8 * (size_t) ctx->cost_log_iter : nullptr, bins);
+                       ctx->phase_log.p ? ctx->phase_log.as<unsigned long long>() + 8 * (size_t) ctx->cost_log_iter : nullptr, bins,
+                       sqrtf(thr_d2) * 1.0001f + 1e-6f);
 }
 
 // stats_mode < 0: search only.  WM_ICP_SVD / WM_ICP_GN6: the search kernel also leaves the ICP

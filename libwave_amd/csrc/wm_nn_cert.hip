@@ -213,31 +213,62 @@ __device__ __forceinline__ void late_wstamp(unsigned long long *dbg_w, unsigned 
 
 template <int STATS, int NB, int RC, bool LATE = false>
 __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_per_eu(4, 4)))
-    k_nn_cert(const LevelsDev *__restrict__ lv, const float4 *__restrict__ src, unsigned n,
+    k_nn_cert(const LevelsDev lv, const LevelsDev *__restrict__ lvp, const float4 *__restrict__ src, unsigned n,
               IcpDevState *__restrict__ st, float thr_d2, unsigned long long *__restrict__ keys,
               float4 *__restrict__ match_pt, float4 *__restrict__ bound, const float4 *__restrict__ tgt_orig,
               float r_light_cells, float lane_lf, float coop_lf, float r0_cells,
               double *__restrict__ partials, int bounds_valid, float pad_mul, float pad_frac,
               unsigned *__restrict__ uns_count, unsigned long long *__restrict__ prof_out, LateArgs la,
-              long long *__restrict__ bins) {
+              long long *__restrict__ bins, float rmax) {
     // (bins != nullptr, launched form only: the workgroup's sums and its count of searched queries are ADDED into
     // the iteration's bins -- exact integer limbs, any order: wm_bins.hpp -- instead of stored as a row of `partials`)
-    // (a wave's life is a chain of memory round trips: the phase's three streams are requested before
-    // anything else is looked at -- their addresses need nothing but the block number)
+    // (a wave's life is a chain of memory round trips, and its start is TWO of them: the kernel arguments -- the level
+    // ladder among them, by value -- and then, requested together, the head run of the state (nn_state, wm_nn_scan.hpp)
+    // and the phase's three streams, whose addresses need nothing but the block number.  The first wait is at the
+    // pin below and `done` is tested behind it (up to eb9ee33 the compiler had that test, a round trip of its own, in
+    // front of the loads): a launch queued behind a `done` has loaded, from clamped indices, and leaves without
+    // storing or adding anything)
+    // (lvp: the ladder's copy in device memory, for a level above 0 chosen at run time.  Looked up in the by-value
+    // copy, as k_nn_grid does, it costs this kernel a stack slot: 20 bytes of scratch where it had none)
+    // (rmax: the search radius that covers the gate, sqrt(thr_d2) with its cushion -- wave-uniform, formed on the host)
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
     const unsigned row = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned gbase = row * (64u * NB * kCertWaves);  // the workgroup's first query
     const unsigned base = gbase + wave * (64u * NB);        // the wave's
+    // (the stream loads' clamp is made to wait for `st` as well: the kernel arguments come in ONE batch and the state
+    // is requested with the streams -- left alone the compiler fetches `st` behind them, one more wait)
+    unsigned n_st = n;
+    asm("" : "+s"(n_st) : "s"(st));
+    const NnState S = nn_state(st);
     float4 p[NB], mp[NB], rf[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-        const unsigned i = min(base + (unsigned) j * 64u + lane, n - 1u);
+        const unsigned i = min(base + (unsigned) j * 64u + lane, n_st - 1u);
         p[j] = src[i];
         mp[j] = match_pt[i];  // (meaningless before the first search, and then not looked at)
         rf[j] = bound[i];
     }
-    if (!LATE && st->done) return;  // (uniform over the workgroup)
+    // the levels' cell sizes (wave-uniform: scalar registers); all six come from the kernel arguments at fixed offsets
+    // -- no address that depends on the depth; the unused ones (0: the host leaves them so) are never looked at (nn_level_for)
+    const int Ln = lv.n;
+    float hl[kMaxLevels];
+#pragma unroll
+    for (int k = 0; k < kMaxLevels; ++k) hl[k] = lv.g[k].h;
+    // (the requests above stay above this line, the first wait below it: the state's words, then the kernel arguments
+    // the searches use)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::WM_NN_STATE_OPERANDS(S), "s"(S.step_disp), "s"(S.changed_mask));
+    asm volatile("" ::"s"(Ln), "s"(hl[0]), "s"(hl[1]), "s"(hl[2]), "s"(hl[3]), "s"(hl[4]), "s"(hl[5]), "s"(r_light_cells),
+                 "s"(lane_lf), "s"(r0_cells), "s"(thr_d2), "s"(rmax));
+    // `done` (uniform over the workgroup) is tested BEHIND phase 1 in the launched form: in front of it the test either
+    // pulls the stream loads behind its branch (the compiler's choice up to eb9ee33: a round trip for `done` alone in
+    // front of the burst) or, with the loads held in front of it, makes phase 1 wait for the last of the twelve loads
+    // before it may touch the first batch (+0.4 us per launch, measured).  Phase 1 writes nothing but this workgroup's
+    // LDS, so a launch queued behind a `done` still stores nothing and adds nothing.
+    if constexpr (LATE) {
+        if (S.done) return;  // (the solver tells the host)
+    }
     // LATE: the three streams of the later iterations come through buffer loads the compiler cannot hoist out
     // of the iteration loop (kept in registers across the searches they would be spilled to scratch: the
     // searches need every register); the match and the bound at agent scope (sc1), past this compute unit's
@@ -259,26 +290,18 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
     __shared__ unsigned s_cnt[kCertWaves];
     __shared__ double s_rows[kCertWaves][kAcc];
     __shared__ float s_bc[20];  // LATE: this iteration's pose, step size, flags, [16] = a wait gave up
-    if constexpr (LATE) {
-        if (st->done) return;  // (a launch queued behind a `done`; the solver tells the host)
-    }
     BalLds &L = s_L[wave];
     s_win[wave][lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kNoIdx));  // (no winner recorded)
-    const int Ln = lv->n;
-    float hl[kMaxLevels];  // the levels' cell sizes (wave-uniform: scalar registers)
-#pragma unroll
-    for (int k = 0; k < kMaxLevels; ++k) hl[k] = lv->g[k < Ln ? k : 0].h;
-    const GridDev g0 = lv->g[0];  // (what the late searches scan: fetched with the rest of the state, not when first needed)
+    const GridDev g0 = lv.g[0];  // (what the late searches scan)
     const float h0 = hl[0];
-    const float rmax = sqrtf(thr_d2) * 1.0001f + 1e-6f;
     const float r_light = r_light_cells * h0;
-    const bool have_prev = st->have_prev != 0;
+    const bool have_prev = S.have_prev != 0;
     // sharded registration: this rank handles the queries whose transformed x lies in its slab (a query
     // it does not own is skipped: no test, no search, nothing stored -- whatever this rank knew about
     // it stays consistent for the day it comes back)
-    const bool slab_on = st->slab_on != 0;
-    const float slab_lo = st->slab_lo, slab_hi = st->slab_hi;
-    const unsigned changed_mask = st->changed_mask;
+    const bool slab_on = S.slab_on != 0;
+    const float slab_lo = S.slab_lo, slab_hi = S.slab_hi;
+    const unsigned changed_mask = S.changed_mask;
     const int comp = acc_comp_of_lane(lane);
     if (stamp_on) pt[1] = clock64();  // state in
     // (LATE: one trip per iteration of the registration; otherwise one trip)
@@ -332,9 +355,9 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
             for (int k = 0; k < 12; ++k)
                 Tl_loc[k] = __uint_as_float((unsigned) __builtin_amdgcn_readfirstlane((int) __float_as_uint(s_bc[k])));
         }
-        const float *Tl = LATE ? Tl_loc : st->Tf;
+        const float *Tl = LATE ? Tl_loc : S.Tf;
         const float step_now = LATE ? __uint_as_float((unsigned) __builtin_amdgcn_readfirstlane((int) __float_as_uint(s_bc[12])))
-                                    : st->step_disp;
+                                    : S.step_disp;
         const bool valid = (LATE && li > 0u) || (bounds_valid != 0 && have_prev);
         // room a search leaves above its result for the runner-up bound: a few of the last step's sizes
         // (what the following steps will add up to while the registration converges)
@@ -430,6 +453,9 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
         if (lane == 0) s_cnt[wave] = n_uns;
         if (stamp_on) pt[3] = clock64();  // phase 1 done
         __syncthreads();
+        if constexpr (!LATE) {
+            if (S.done) return;  // (a launch queued behind a `done`: nothing stored, nothing added -- see the top)
+        }
         late_wstamp<LATE>(la.dbg_w, la.dbg_li, li, 1);  // phase 1 done (all waves)
         // ---- phase 2: what is left in the workgroup, 64 queries at a time, chunk c by wave c mod 4
         unsigned cum[kCertWaves + 1];
@@ -523,7 +549,9 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                             bqx = tp.x;
                             bqy = tp.y;
                             bqz = tp.z;
-                            const float sd = sqrtf(d2b);
+                            // (v_sqrt_f32, 1 ulp: the cushion of 1e-4 relative + 1e-6 m below covers it, as in phase 1;
+                            // the pad is whatever it comes to here: the radius and the bound use the same one)
+                            const float sd = __builtin_amdgcn_sqrtf(d2b);
                             pad = fminf(pad_room, pad_frac * sd);
                             r = fmaxf(sd * 1.0001f + 1e-6f, 0.05f * h0) + pad;
                         }
@@ -553,12 +581,12 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 const int l0 = __builtin_amdgcn_readlane(l, __ffsll((long long) lv_mask) - 1);
                 float margin;
                 if (__ballot(live && l != l0) == 0ull) {
-                    const GridDev g = l0 == 0 ? g0 : lv->g[l0];
+                    const GridDev g = l0 == 0 ? g0 : lvp->g[l0];
                     if (!scan_box_rows(g, live, qx, qy, qz, r, best, &margin, L, lane, &bnd))
                         best = scan_box_bal<false, RC, true>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev,
                                                               g.pts, cost, prof, &bnd);
                 } else {
-                    const GridDev g = lv->g[l];
+                    const GridDev g = lvp->g[l];
                     L.base[lane] = (unsigned long long) g.pts;
                     best = scan_box_bal<false, RC, true>(g, live, qx, qy, qz, r, best, &margin, L, lane, have_prev,
                                                           nullptr, cost, prof, &bnd);
@@ -592,9 +620,8 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 const float upad = rl_f(pad, sl);
                 if ((unsigned) ub == kNoIdx && seed > ur) ur = fminf(seed, rmax);
                 for (int pass = 0; pass < 64; ++pass) {
-                    int l = 0;
-                    while (l < Ln - 1 && lv->g[l].h < coop_lf * ur) ++l;
-                    const GridDev g = lv->g[l];
+                    const int l = nn_level_for(hl, Ln, coop_lf, ur);
+                    const GridDev g = lvp->g[l];
                     float margin;
                     ub = coop_scan_box(g, ux, uy, uz, ur, ub, lane, &margin, &usec, upad);
                     umargin = margin;
@@ -737,7 +764,7 @@ static void launch_cert_kernel(wm_ctx *ctx, unsigned blocks, float thr_d2, bool 
                                long long *bins) {
     const bool log = !LATE && ctx->cert_log_iter < ctx->cert_log_cap;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_cert<STATS, NB, 3, LATE>), dim3(blocks), dim3(64 * kCertWaves), 0, ctx->stream,
-                       ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
+                       ctx->levels_dev, ctx->d_levels.as<LevelsDev>(), ctx->src_sorted.as<float4>(), (unsigned) ctx->n_src,
                        ctx->d_state.as<IcpDevState>(), thr_d2, ctx->keys.as<unsigned long long>(),
                        ctx->match_pt.as<float4>(), ctx->nn_bound.as<float4>(), ctx->tgt_orig.as<float4>(),
                        ctx->tune_r_light, ctx->tune_lane_lf, ctx->tune_coop_lf, ctx->tune_r0,
@@ -746,7 +773,7 @@ static void launch_cert_kernel(wm_ctx *ctx, unsigned blocks, float thr_d2, bool 
                        log && ctx->cert_count.p ? ctx->cert_count.as<unsigned>() + 64 * (size_t) ctx->cert_log_iter : nullptr,
                        log && ctx->cert_prof.p ? ctx->cert_prof.as<unsigned long long>() + 64 * (size_t) ctx->cert_log_iter
                                                : nullptr,
-                       la, bins);
+                       la, bins, sqrtf(thr_d2) * 1.0001f + 1e-6f);
 }
 
 // use_bins (with a stats_mode): sums and the searched-queries count go into the iteration's bins (wm_bins.hpp) --

@@ -48,6 +48,40 @@ __device__ __forceinline__ unsigned xcd_remap_chunked(unsigned b, unsigned S) {
     return (chunk * 8u + x) * S + (l - chunk * S);
 }
 
+// ------------------------------------------------- what a search wave needs of the state before it can start
+// The head run of IcpDevState (wm_internal.hpp), read through a uniform pointer: two wide scalar loads, requested
+// together with the wave's stream loads.  Each kernel has ONE empty asm statement where the wave first waits: it names
+// these words as scalar operands (WM_NN_STATE_OPERANDS) -- in k_nn_grid next to the stream loads' registers, in
+// k_nn_cert behind a scheduling barrier that keeps the burst above it -- so the compiler can neither put the test of
+// `done` in front of the requests (it did, sinking every load behind that branch and making a round trip of each) nor
+// fetch a word later, when it is first used.  scripts/dev/nn_prologue_report.py reads the outcome off the code object.
+struct NnState {
+    float Tf[12];
+    int done, have_prev, slab_on;
+    float slab_lo, slab_hi;
+    unsigned changed_mask;
+    float step_disp;
+};
+__device__ __forceinline__ NnState nn_state(const IcpDevState *st) {
+    NnState s;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) s.Tf[k] = st->Tf[k];
+    s.done = st->done;
+    s.have_prev = st->have_prev;
+    s.slab_on = st->slab_on;
+    s.slab_lo = st->slab_lo;
+    s.slab_hi = st->slab_hi;
+    s.changed_mask = st->changed_mask;
+    s.step_disp = st->step_disp;
+    return s;
+}
+// (the scalar operands of that statement: 17 of an asm statement's 30; the last two words of the run arrive in the
+// load that brings slab_hi)
+#define WM_NN_STATE_OPERANDS(s)                                                                                              \
+    "s"((s).Tf[0]), "s"((s).Tf[1]), "s"((s).Tf[2]), "s"((s).Tf[3]), "s"((s).Tf[4]), "s"((s).Tf[5]), "s"((s).Tf[6]),           \
+        "s"((s).Tf[7]), "s"((s).Tf[8]), "s"((s).Tf[9]), "s"((s).Tf[10]), "s"((s).Tf[11]), "s"((s).done), "s"((s).have_prev), \
+        "s"((s).slab_on), "s"((s).slab_lo), "s"((s).slab_hi)
+
 // The grid tables are reached through pointers read from memory, so the compiler only knows
 // them as generic (flat) addresses; they always point into HBM -- say so, and get global_load
 // instead of flat_load (no LDS-aperture check, no lgkmcnt coupling).
@@ -820,8 +854,10 @@ __device__ __forceinline__ bool nn_certified(float margin, float bd2, float thr_
 // Not certified: the radius must GROW (a query sitting on a cell face can have a non-positive margin however small
 // its neighbour distance is): to the best distance found (+ pad, the room k_nn_cert's runner-up bound wants; 0.f is
 // the same bits as none: the sum it joins is >= 1e-6, never -0), or to 2 r when nothing was found; by a quarter at least
+// (v_sqrt_f32, 1 ulp = 6e-8 relative: the cushion of 1e-4 relative + 1e-6 m covers it, as in k_nn_cert's phase 1; a
+// radius steers work, never a result)
 __device__ __forceinline__ float nn_grow_radius(unsigned long long best, float bd2, float r, float rmax, float pad = 0.f) {
-    const float rn = ((unsigned) best != kNoIdx) ? sqrtf(bd2) * 1.0001f + 1e-6f + pad : 2.0f * r;
+    const float rn = ((unsigned) best != kNoIdx) ? __builtin_amdgcn_sqrtf(bd2) * 1.0001f + 1e-6f + pad : 2.0f * r;
     return fminf(fmaxf(rn, 1.25f * r), rmax);
 }
 // the finest level whose cell is >= lf * r (cell sizes double from level to level; hl: the levels' cell sizes)
