@@ -348,7 +348,8 @@ int wm_debug_solve_cycles(wm_ctx *ctx, unsigned long long out[8]);
 /* Developer aid: per-query work of the grid search.  out == NULL arms the log for the first
  * `iterations` iterations of the next wm_icp_align on the current clouds (0 disarms and frees it);
  * out != NULL copies the log ([iteration][query in Morton order]: trips of the candidate loop in
- * bits 0-15, row chunks in bits 16-23, scan passes in bits 24-30, bit 31 = handed to the
+ * bits 0-15, row chunks in bits 16-23, scan passes in bits 24-27 (saturating), rungs of the radius
+ * probe of a query that had no candidate in bits 28-30 (saturating), bit 31 = handed to the
  * wave-cooperative path) and returns the number of iterations recorded. */
 int wm_debug_cost_log(wm_ctx *ctx, int iterations, unsigned *out, size_t cap);
 /* with the cost log armed: per iteration, shader-clock cycle sums over the waves of the search kernel's

@@ -26,8 +26,9 @@ namespace wm {
 // One lane per query: a certified radius search over a ladder of uniform grids
 // (cell size x2 per level).
 //   r <- the distance, under the NEW pose, to the point this query matched in the previous
-//        iteration (a real candidate, so an upper bound of the answer); half a fine cell when
-//        there is none;
+//        iteration (a real candidate, so an upper bound of the answer); when there is none (the first search): the
+//        distance to one point of the first box of the ladder half a fine cell, x2, x2, ... that holds any -- found by
+//        probing the boxes' occupancy on coarse levels, not by walking them (balanced walk; the lane scan walks the ladder);
 //   repeat: scan ball(q, min(r, sqrt(best))) inside the box of cells covering [q - r, q + r]^3,
 //           on the finest level whose cell is >= lane_lf * r (0.2 r: many short rows, each cut
 //           to the ball's chord); certified when best <= margin(box) or the box already covers
@@ -95,7 +96,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
     __shared__ BalHolder<BAL> s_hold;
     const int L_levels = L;
     const float h0 = hl[0];
-    const float r_light = r_light_cells * h0;  // larger radii go to the cooperative path
+    // larger radii go to the cooperative path.  (Formed again at every use, from the two scalars: there is no scalar
+    // float multiply, and kept in a vector register through the whole search it was one the compiler spilled to scratch)
+    auto r_light = [&]() -> float {
+        float c = r_light_cells;
+        asm volatile("" : "+s"(c));
+        return c * h0;
+    };
     const bool have_prev = S.have_prev != 0;  // wave-uniform
     float qx = 0.f, qy = 0.f, qz = 0.f, r = 0.f;
     float bqx = 0.f, bqy = 0.f, bqz = 0.f;  // coordinates of the previous iteration's match
@@ -138,7 +145,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
             }
         }
         r = fminf(r, rmax);
-        heavy = r > r_light;
+        heavy = r > r_light();
     }
     const unsigned long long prof_pro = COST ? clock64() : 0ull;
     if constexpr (BAL) {
@@ -154,6 +161,52 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
         // (big boxes are walked by layers in unseeded searches too: nearest-first, the walk has a candidate to cut
         // its rows with after the first chunks -- iteration 0 of the 1M pair 466 -> 367 us)
         const bool allow_layered = true;
+        // A lane with nothing to start from finds its radius by PROBING, not by walking: the rungs of its ladder
+        // (r0 cells, x2 per rung -- the radii the passes below would try in turn) are tested for an empty box on the
+        // coarsest level whose cell is <= the rung (probe_box_empty: a round trip of cell_start look-ups per rung, no
+        // candidate trips).  An empty probe box contains the box a pass at that radius would have walked, so only
+        // passes that would have found nothing are left out.  At the first rung whose box holds a point the lane
+        // FETCHES one -- the middle point of a central row of the box -- and, if that is inside the gate and within
+        // the lane scan's reach, starts like a seeded query: the point is its candidate and its distance the radius
+        // of a pass that is certain to certify, its rows cut to the ball from the first chunk (without a candidate
+        // the first pass walked uncut rows until it met a point, certified for 44 % of the queries of the 1M pair,
+        // and a second pass walked the ball again for the rest).  A candidate out of reach changes nothing: the
+        // lane's first pass is made at the rung's radius, as the ladder would have.  Radii and candidates steer work,
+        // never a result, and the lanes that end up heavy are the ladder's.  A seeded launch pays the ballot (a lane
+        // whose previous match is out of range starts at rmax and is not probed).
+        bool probing = live && (unsigned) best == kNoIdx && r < rmax;
+        if (__ballot(probing) != 0ull) {
+            float rp = r0_cells * h0;  // the rung: every probing lane's r (wave-uniform)
+            for (int rung = 0; rung < 16 && __ballot(probing) != 0ull; ++rung) {
+                int lp = 0;
+#pragma unroll
+                for (int k = 1; k < kMaxLevels; ++k) lp += (k < L_levels && hl[k] <= rp) ? 1 : 0;
+                const GridDev g = lv.g[lp];
+                unsigned cand;  // a place in g.pts (below the level's point count: a row that holds points)
+                const bool empty = probe_box_empty(g, probing, qx, qy, qz, rp, cand);
+                const bool hit = probing && !empty;
+                const f4v ct = ((gp_f4) g.pts)[hit ? cand : 0u];
+                if (hit) {
+                    // (a NaN target point fails the comparison; the radius is formed as a seeded query's is)
+                    const float d2c = canon_d2v(qx, qy, qz, ct);
+                    const float rc = fmaxf(__builtin_amdgcn_sqrtf(d2c) * 1.0001f + 1e-6f, 0.05f * h0);
+                    if (d2c <= thr_d2 && rc <= r_light()) {
+                        best = make_key(d2c, __float_as_uint(ct.w));
+                        r = fminf(rc, rmax);
+                    }
+                }
+                if (probing) {
+                    if constexpr (COST) cost += ((cost >> 28) & 7u) < 7u ? 1u << 28 : 0u;  // probe rungs: bits 28-30
+                    if (empty) {
+                        r = nn_grow_radius(best, 0.f, r, rmax);
+                        heavy = r > r_light();
+                        live = !heavy;
+                    }
+                    probing = empty && live && r < rmax;
+                }
+                rp = fminf(2.0f * rp, rmax);
+            }
+        }
         for (int pass = 0; pass < 32 && __ballot(live) != 0ull; ++pass) {
             const int l = nn_level_for(hl, L_levels, lane_lf, r);
             // all live lanes on one level (always, once the clouds are close): the level's
@@ -172,13 +225,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
                 best = scan_box_bal<COST, kBalRowChunk>(g, live, qx, qy, qz, r, best, &margin, L, lane, allow_layered, nullptr, cost, prof);
             }
             if (live) {
-                if constexpr (COST) cost += 1u << 24;
+                if constexpr (COST) cost += ((cost >> 24) & 15u) < 15u ? 1u << 24 : 0u;  // passes: bits 24-27
                 const float bd2 = __uint_as_float((unsigned) (best >> 32));
                 if (nn_certified(margin, bd2, thr_d2)) {
                     live = false;
                 } else {
                     r = nn_grow_radius(best, bd2, r, rmax);
-                    heavy = r > r_light;
+                    heavy = r > r_light();
                     live = !heavy;
                 }
             }
@@ -189,13 +242,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
             const GridDev g = lv.g[l];
             float margin;
             best = scan_box<COST>(g, qx, qy, qz, r, best, &margin, s_runs, lane, have_prev, cost);
-            if constexpr (COST) cost += 1u << 24;  // passes
+            if constexpr (COST) cost += ((cost >> 24) & 15u) < 15u ? 1u << 24 : 0u;  // passes: bits 24-27
             const float bd2 = __uint_as_float((unsigned) (best >> 32));
             if (nn_certified(margin, bd2, thr_d2)) break;
             // not certified: the radius must GROW (a query sitting on a cell face can have a
             // non-positive margin however small its neighbour distance is)
             r = nn_grow_radius(best, bd2, r, rmax);
-            heavy = r > r_light;
+            heavy = r > r_light();
         }
     }
     const unsigned long long prof_pass = COST ? clock64() : 0ull;

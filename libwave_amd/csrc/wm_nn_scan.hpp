@@ -633,6 +633,83 @@ __device__ __forceinline__ unsigned long long scan_box_bal(const GridDev &g, boo
     return best;
 }
 
+// Occupancy probe: does the box scan_box_bal would walk for radius r on level g -- floor(f +- (r inv_h + slack)),
+// clamped to the lattice -- hold any target point at all?  Answered from cell_start alone: a (y,z) row of the box is
+// one contiguous run of the cell-sorted array, so the two look-ups the walk makes per row give the row's point count,
+// and no candidate is touched.  The box covers ball(q, r) by the very argument that certifies a scan of it (every
+// level's cells are the level-0 cells shifted right: derive_grid_level, clamped at the lattice's last, possibly
+// partial, cell exactly as the points' own cells are), so "empty" means: no target point within r of the query.
+// A lane without a candidate uses it to find the radius at which a walk first has something to find (k_nn_grid),
+// on a level whose cell is about r: a box of some 3 x 3 rows -- kProbeRows pairs of look-ups, one memory round
+// trip -- where the walk's own level has 25 or 81.  A non-empty box also names one of its points (`cand`), for the
+// lane to start its walk from.
+constexpr int kProbeRows = 9;
+struct ProbeBox {  // one lane's box on one level, and its row cursor
+    int xa, xb, ya, yb, zb, yy, zz;
+    unsigned found;  // != 0: a row of the box holds a point
+    unsigned cand;   // a point (place in g.pts) of a non-empty row
+    __device__ __forceinline__ ProbeBox(const GridDev &g, bool probing, float qx, float qy, float qz, float r) {
+        const float big = 4.0e6f;
+        const float fx = fminf(fmaxf((qx - g.ox) * g.inv_h, -big), big);
+        const float fy = fminf(fmaxf((qy - g.oy) * g.inv_h, -big), big);
+        const float fz = fminf(fmaxf((qz - g.oz) * g.inv_h, -big), big);
+        const float rc = r * g.inv_h + g.slack;
+        xa = max((int) floorf(fx - rc), 0), xb = min((int) floorf(fx + rc), g.nx - 1);
+        ya = max((int) floorf(fy - rc), 0), yb = min((int) floorf(fy + rc), g.ny - 1);
+        const int za = max((int) floorf(fz - rc), 0);
+        zb = min((int) floorf(fz + rc), g.nz - 1);
+        const bool has = probing && !(xa > xb || ya > yb || za > zb);
+        found = 0u;
+        cand = 0u;
+        yy = ya, zz = has ? za : zb + 1;  // (a lane without rows is past its last one)
+    }
+    __device__ __forceinline__ bool more() const { return zz <= zb && found == 0u; }
+    // the next kProbeRows rows' look-ups (cell_start[0] twice for a row that does not exist), all requested together
+    __device__ __forceinline__ void request(const GridDev &g, unsigned (&rs)[kProbeRows], unsigned (&re)[kProbeRows]) {
+        unsigned a0[kProbeRows], a1[kProbeRows];
+        const bool go = found == 0u;
+#pragma unroll
+        for (int u = 0; u < kProbeRows; ++u) {
+            const bool ok = go && zz <= zb;
+            const unsigned base = ((unsigned) zz * g.ny + yy) * g.nx;
+            a0[u] = ok ? base + xa : 0u;
+            a1[u] = ok ? base + xb + 1 : 0u;
+            const bool wrap = yy >= yb;
+            yy = wrap ? ya : yy + 1;
+            zz += (wrap && zz <= zb) ? 1 : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < kProbeRows; ++u) {
+            rs[u] = ldc(g.cell_start, a0[u]);
+            re[u] = ldc(g.cell_start, a1[u]);
+        }
+    }
+    __device__ __forceinline__ void take(const unsigned (&rs)[kProbeRows], const unsigned (&re)[kProbeRows]) {
+#pragma unroll
+        for (int u = 0; u < kProbeRows; ++u) found |= re[u] - rs[u];  // (cell_start ascends: a difference is a count)
+        // the middle point of a non-empty row, the box's central rows preferred (3 x 3: centre, edges, corners)
+        const int order[kProbeRows] = {8, 6, 2, 0, 7, 5, 3, 1, 4};
+#pragma unroll
+        for (int k = 0; k < kProbeRows; ++k) {
+            const int u = order[k];
+            if (re[u] != rs[u]) cand = (rs[u] + re[u]) >> 1;
+        }
+    }
+};
+// One rung of a lane's radius ladder: is box (g, r) empty (if not: cand = the place in g.pts of one of its points)?
+// Wave-uniform loop (one trip for a box of up to kProbeRows rows): lanes that are not probing, are done with their
+// rows or have met a point contribute look-ups of cell_start[0].
+__device__ __forceinline__ bool probe_box_empty(const GridDev &g, bool probing, float qx, float qy, float qz, float r, unsigned &cand) {
+    ProbeBox b(g, probing, qx, qy, qz, r);
+    while (__ballot(b.more()) != 0ull) {
+        unsigned rs[kProbeRows], re[kProbeRows];
+        b.request(g, rs, re);
+        b.take(rs, re);
+    }
+    cand = b.cand;
+    return b.found == 0u;
+}
+
 // The same scan for a wave with FEW searches going (the certificate kernel's late iterations: a
 // handful of unsettled queries per wave, boxes of one to nine rows).  scan_box_bal makes every lane
 // step through its own rows three at a time, so a wave with five live lanes still pays a full step

@@ -46,7 +46,8 @@ for i in (0, 1, 3, 8, 14, 30, 49):
 print("iterations logged", log.shape)
 trips = (log & 0xFFFF).astype(np.int64)
 chunks = ((log >> 16) & 0xFF).astype(np.int64)
-passes = ((log >> 24) & 0x7F).astype(np.int64)
+passes = ((log >> 24) & 0xF).astype(np.int64)   # (saturates at 15)
+rungs = ((log >> 28) & 0x7).astype(np.int64)    # probe rungs of a query without a candidate (saturates at 7)
 heavy = (log >> 31).astype(np.int64)
 pad = (-n) % 2048
 
@@ -71,7 +72,7 @@ coef, *_ = np.linalg.lstsq(X[1:], t_us[1:ITERS], rcond=None)  # iteration 0 (uns
 pred = X @ coef
 print("fit: t_us = %.3e * sum_max_trips + %.3e * sum_max_chunks + %.2f ; residual rms %.2f us" % (
     coef[0], coef[1], coef[2], float(np.sqrt(np.mean((pred[1:] - t_us[1:ITERS]) ** 2)))))
-print("it  t_us  pred | lane-eff trips chunks | passes>1  heavy | trips/q chunks/q | ideal-bin  prev-bin (pred us)")
+print("it  t_us  pred | lane-eff trips chunks | passes>1  heavy | passes/q rungs/q trips/q chunks/q | ideal-bin  prev-bin (pred us)")
 tot = dict(cur=0.0, ideal=0.0, prev=0.0, meas=0.0)
 for i in range(ITERS):
     tr, ch = trips[i], chunks[i]
@@ -89,9 +90,9 @@ for i in range(ITERS):
         prevb = pred[i]
     tot["cur"] += pred[i]; tot["ideal"] += ideal; tot["prev"] += prevb; tot["meas"] += t_us[i]
     if i < 16 or i % 8 == 0 or i == ITERS - 1:
-        print("%2d %6.1f %6.1f | %.2f %.2f | %.4f %.5f | %.2f %.2f | %6.1f %6.1f" % (
+        print("%2d %6.1f %6.1f | %.2f %.2f | %.4f %.5f | %.2f %.2f %.2f %.2f | %6.1f %6.1f" % (
             i, t_us[i], pred[i], eff_t, eff_c, float((passes[i] > 1).mean()), float(heavy[i].mean()),
-            tr.mean(), ch.mean(), ideal, prevb))
+            passes[i].mean(), rungs[i].mean(), tr.mean(), ch.mean(), ideal, prevb))
 print("sum over iterations (us): measured %.0f, model %.0f, ideal binning %.0f, previous-iteration binning %.0f" % (
     tot["meas"], tot["cur"], tot["ideal"], tot["prev"]))
 # distribution of the aligned state

@@ -1,5 +1,5 @@
 """Where the first (unseeded) search and the early seeded ones spend their work: per-query passes,
-row chunks and trips (wm_debug_cost_log) against the query's true neighbour distance."""
+probe rungs, row chunks and trips (wm_debug_cost_log) against the query's true neighbour distance."""
 import os
 import sys
 
@@ -26,9 +26,11 @@ for it in range(len(log)):
     c = log[it]
     trips = (c & 0xFFFF).astype(np.int64)
     chunks = ((c >> 16) & 0xFF).astype(np.int64)
-    passes = ((c >> 24) & 0x7F).astype(np.int64)
+    passes = ((c >> 24) & 0xF).astype(np.int64)
+    rungs = ((c >> 28) & 0x7).astype(np.int64)
     heavy = (c >> 31).astype(np.int64)
-    print("it %d: heavy %d | passes hist %s" % (it, heavy.sum(), np.bincount(passes, minlength=8)[:10]))
+    print("it %d: heavy %d | passes hist %s | probe rungs hist %s" % (it, heavy.sum(), np.bincount(passes, minlength=8)[:10],
+                                                                       np.bincount(rungs, minlength=8)))
     for p in range(1, 8):
         m = passes == p
         if m.sum():

@@ -65,7 +65,7 @@ for pattern in ("default", "rings"):
     for it in range(len(log)):
         c = log[it]
         trips, chunks = (c & 0xFFFF).astype(np.int64), ((c >> 16) & 0xFF).astype(np.int64)
-        passes = ((c >> 24) & 0x7F).astype(np.int64)
+        passes = ((c >> 24) & 0xF).astype(np.int64)  # (bits 28-30: probe rungs)
         w = np.pad(chunks, (0, (-n) % 64)).reshape(-1, 64)
         t = np.pad(trips, (0, (-n) % 64)).reshape(-1, 64)
         print("  it %d: chunks/query %.2f, trips/query %.2f | per wave: max-lane chunks %.1f, trips/64 %.1f | heavy %d" % (
