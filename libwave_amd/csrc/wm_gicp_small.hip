@@ -24,6 +24,8 @@
 #include "wm_gicp_dev.hpp"
 #include "wm_bfgs.hpp"
 #include "wm_gicp_quad.hpp"
+#include "wm_pair_terms.hpp"
+#include "wm_wave.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -148,12 +150,6 @@ __device__ __forceinline__ double gs_quad_term(const GsQuadLds &G, int c, unsign
 }
 
 
-__device__ __forceinline__ bool gs_load(const unsigned char *base, unsigned i, unsigned stride, float &x, float &y, float &z) {
-    const float *p = reinterpret_cast<const float *>(base + (size_t) i * stride);
-    x = p[0], y = p[1], z = p[2];
-    return x - x == 0.f && y - y == 0.f && z - z == 0.f;  // finite
-}
-
 __device__ __forceinline__ unsigned gs_cell(const GridDev &g, float x, float y, float z) {
     int cx = (int) floorf((x - g.ox) * g.inv_h), cy = (int) floorf((y - g.oy) * g.inv_h), cz = (int) floorf((z - g.oz) * g.inv_h);
     cx = min(max(cx, 0), g.nx - 1);
@@ -179,7 +175,7 @@ __device__ __attribute__((noinline)) unsigned gs_build_grid(const unsigned char 
     unsigned cnt = 0;
     for (unsigned i = tid; i < n; i += kGsThreads) {
         float x, y, z;
-        if (gs_load(raw, i, stride, x, y, z)) {
+        if (load_point_finite(raw, i, stride, x, y, z)) {
             lo[0] = fminf(lo[0], x), lo[1] = fminf(lo[1], y), lo[2] = fminf(lo[2], z);
             hi[0] = fmaxf(hi[0], x), hi[1] = fmaxf(hi[1], y), hi[2] = fmaxf(hi[2], z);
             ++cnt;
@@ -247,7 +243,7 @@ __device__ __attribute__((noinline)) unsigned gs_build_grid(const unsigned char 
         __syncthreads();
         for (unsigned i = tid; i < n; i += kGsThreads) {
             float x, y, z;
-            if (gs_load(raw, i, stride, x, y, z)) atomicAdd(&run[gs_cell(g, x, y, z)], 1u);
+            if (load_point_finite(raw, i, stride, x, y, z)) atomicAdd(&run[gs_cell(g, x, y, z)], 1u);
         }
         __syncthreads();
         if (attempt == 1) break;
@@ -269,43 +265,12 @@ __device__ __attribute__((noinline)) unsigned gs_build_grid(const unsigned char 
         if (!(h_new < 0.9f * h)) break;
         h = h_new;
     }
-    // exclusive scan of the counts, 4096 cells (four per thread) at a time: run[c] and cs[c] = the cell's first slot
-    unsigned carry = 0;
-    for (unsigned c0 = 0; c0 < cells; c0 += 4u * kGsThreads) {
-        const unsigned c = c0 + 4u * tid;
-        unsigned v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = c + (unsigned) u < cells ? __hip_atomic_load(&run[c + (unsigned) u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const unsigned mine = v[0] + v[1] + v[2] + v[3];
-        unsigned incl = mine;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned up = __shfl_up(incl, m);
-            if ((int) lane >= m) incl += up;
-        }
-        if (lane == 63) S.scan[wave] = incl;
-        __syncthreads();
-        unsigned base = carry, all = 0;
-        for (unsigned w = 0; w < (unsigned) kGsWaves; ++w) {
-            if (w < wave) base += S.scan[w];
-            all += S.scan[w];
-        }
-        unsigned at = base + incl - mine;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (c + (unsigned) u < cells) {
-                run[c + (unsigned) u] = at;
-                cs[c + (unsigned) u] = at;
-                at += v[u];
-            }
-        carry += all;
-        __syncthreads();
-    }
+    block_scan_counts<kGsThreads>(run, cs, cells, S.scan);  // run[c] and cs[c] = the cell's first slot
     if (tid == 0) cs[cells] = n_valid;
     __syncthreads();
     for (unsigned i = tid; i < n; i += kGsThreads) {
         float x, y, z;
-        if (gs_load(raw, i, stride, x, y, z)) {
+        if (load_point_finite(raw, i, stride, x, y, z)) {
             const unsigned pos = atomicAdd(&run[gs_cell(g, x, y, z)], 1u);
             pts[pos] = make_float4(x, y, z, __uint_as_float(i));
         }
@@ -442,7 +407,7 @@ __device__ __attribute__((noinline)) void gs_covariances(GsShared &S, uint2 *run
             knn_search<K>(g, q.x, q.y, q.z, k, k <= 12 ? 1.0f : 1.5f, best, runs, tid, kGsThreads);
             gicp_cov_of_list<K>(best, k, eps, [&](unsigned idx) {
                 float x, y, z;
-                (void) gs_load(raw, idx, stride, x, y, z);
+                (void) load_point_finite(raw, idx, stride, x, y, z);
                 return make_float4(x, y, z, 0.f);
             }, cov + (size_t) __float_as_uint(q.w) * 9);
         }
@@ -494,10 +459,8 @@ __device__ __attribute__((noinline)) void gs_correspondences(GsShared &S, uint2 
         if constexpr (STATS) G->ok[tid] = 0u;
         if (i < n_s) {
         const float4 p = s_pts[i];
-        // PCL's float transform of a source point: ((m00*x + m01*y) + m02*z) + m03
-        const float qx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)), __fmul_rn(T[2], p.z)), T[3]);
-        const float qy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)), __fmul_rn(T[6], p.z)), T[7]);
-        const float qz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)), __fmul_rn(T[10], p.z)), T[11]);
+        float qx, qy, qz;
+        xform_pcl(T, p.x, p.y, p.z, qx, qy, qz);
         unsigned long long best[1];
         if (debug & 4) best[0] = i < n_t ? (unsigned long long) __float_as_uint(gt.pts[i].w) : ~0ull;  // (developer timing experiment: no search)
         else knn_search<1>(gt, qx, qy, qz, 1, 0.5f, best, runs, tid, kGsThreads, r_stop);
@@ -506,7 +469,7 @@ __device__ __attribute__((noinline)) void gs_correspondences(GsShared &S, uint2 
         match[i] = j;
         if (j != kNoIdx) {
             float x, y, z;
-            (void) gs_load(tgt, j, stride, x, y, z);
+            (void) load_point_finite(tgt, j, stride, x, y, z);
             double R[9];
 #pragma unroll
             for (int a = 0; a < 3; ++a)

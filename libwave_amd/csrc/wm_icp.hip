@@ -18,6 +18,7 @@
 //      the RCCL all-reduce carries between (2) and (3).
 #include "wm_internal.hpp"
 #include "wm_icp_step.hpp"
+#include "wm_pair_terms.hpp"
 #include "wm_bins.hpp"
 #include "wm_xchg.hpp"
 
@@ -35,16 +36,6 @@ namespace wm {
 
 constexpr int kMaxStatBlocks = 256;
 constexpr int kStatUnroll = 4;  // points per thread per trip of the statistics kernel
-
-__device__ __forceinline__ void xform_pt(const float *T, const float4 &p, float &x, float &y,
-                                         float &z) {
-    x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)),
-                            __fmul_rn(T[2], p.z)), T[3]);
-    y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)),
-                            __fmul_rn(T[6], p.z)), T[7]);
-    z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)),
-                            __fmul_rn(T[10], p.z)), T[11]);
-}
 
 // Per-workgroup partial sums, written as partials[block][kAcc].
 template <int MODE>
@@ -79,51 +70,16 @@ __global__ void __launch_bounds__(kBlock)
         for (int u = 0; u < kStatUnroll; ++u) {
             if (i0 + u * stride >= n) break;
             float fx, fy, fz;
-            xform_pt(st->Tf, p4v[u], fx, fy, fz);
+            xform_pcl(st->Tf, p4v[u].x, p4v[u].y, p4v[u].z, fx, fy, fz);
             // sharded registration: the same ownership test as the search kernel
             if (slab_on && !(fx >= slab_lo && fx < slab_hi)) continue;
             a[17] += 1.0;
             const unsigned long long key = keyv[u];
-            const unsigned idx = (unsigned) key;
-            if (idx == kNoIdx) continue;
+            if ((unsigned) key == kNoIdx) continue;
             if ((int) (unsigned) (key >> 32) > rej_thr) continue;  // rejected
-            const float4 q4 = q4v[u];
-            const double px = fx, py = fy, pz = fz, qx = q4.x, qy = q4.y, qz = q4.z;
-            const double d2 = (double) __uint_as_float((unsigned) (key >> 32));
-            a[0] += 1.0;
-            a[1] += px;
-            a[2] += py;
-            a[3] += pz;
-            if (MODE == WM_ICP_SVD) {
-                a[4] += qx;
-                a[5] += qy;
-                a[6] += qz;
-                a[7] += qx * px;
-                a[8] += qx * py;
-                a[9] += qx * pz;
-                a[10] += qy * px;
-                a[11] += qy * py;
-                a[12] += qy * pz;
-                a[13] += qz * px;
-                a[14] += qz * py;
-                a[15] += qz * pz;
-            } else {
-                const double rx = px - qx, ry = py - qy, rz = pz - qz;
-                a[4] += py * py + pz * pz;  // (A^T A)(0,0)
-                a[5] += -px * py;           // (0,1)
-                a[6] += -px * pz;           // (0,2)
-                a[7] += px * px + pz * pz;  // (1,1)
-                a[8] += -py * pz;           // (1,2)
-                a[9] += px * px + py * py;  // (2,2)
-                a[10] += rx;
-                a[11] += ry;
-                a[12] += rz;
-                a[13] += py * rz - pz * ry;  // p x r
-                a[14] += pz * rx - px * rz;
-                a[15] += px * ry - py * rx;
-            }
-            a[16] += d2;
-    }
+            icp_pair_terms<MODE>(fx, fy, fz, q4v[u].x, q4v[u].y, q4v[u].z, __uint_as_float((unsigned) (key >> 32)),
+                                 [&](int k, double term) { a[k] += term; });
+        }
     }
     // wave reduction (fixed xor-tree order), then across the 4 waves through LDS
 #pragma unroll

@@ -10,6 +10,7 @@
 // themselves run in double in a fixed tree order (the reference sums sequentially,
 // and its s^2 in float -- a ~1e-5 relative difference, documented in DESIGN.md).
 #include "wm_internal.hpp"
+#include "wm_pair_terms.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -19,16 +20,6 @@ namespace wm {
 
 constexpr int kInfoAcc = 48;
 constexpr int kInfoBlocks = 512;
-
-__device__ __forceinline__ void xform_f(const float *T, const float4 &p, float &x, float &y,
-                                        float &z) {
-    x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)),
-                            __fmul_rn(T[2], p.z)), T[3]);
-    y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)),
-                            __fmul_rn(T[6], p.z)), T[7]);
-    z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)),
-                            __fmul_rn(T[10], p.z)), T[11]);
-}
 
 template <int NACC>
 __device__ __forceinline__ void block_reduce_store(double *a, double *partials) {
@@ -65,12 +56,11 @@ struct InfoArgs {
 __device__ __forceinline__ bool info_owned(const InfoArgs &A, const float4 &p) {
     if (!A.slab_on) return true;
     float gx, gy, gz;
-    xform_f(A.Tg, p, gx, gy, gz);
+    xform_pcl(A.Tg, p.x, p.y, p.z, gx, gy, gz);
     return gx >= A.slab_lo && gx < A.slab_hi;
 }
 
-// pass 1: a[0]=n, a[1..3]=sum av, a[4..9]=MM(3,4),(3,5),(4,5),(3,3),(4,4),(5,5) terms,
-//         a[10..15]=MZ(0..5)
+// pass 1: the sums of lum_terms (wm_pair_terms.hpp)
 __global__ void __launch_bounds__(kBlock)
     k_lum_sums(const float4 *__restrict__ src, unsigned n,
                const unsigned long long *__restrict__ keys, const float4 *__restrict__ tgt,
@@ -81,28 +71,11 @@ __global__ void __launch_bounds__(kBlock)
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const unsigned idx = (unsigned) keys[i];
         if (idx == kNoIdx || !info_owned(A, src[i])) continue;
+        const float4 p = src[i];
         float px, py, pz;
-        xform_f(A.Tf, src[i], px, py, pz);
+        xform_pcl(A.Tf, p.x, p.y, p.z, px, py, pz);
         const float4 q = tgt[idx];
-        const float av0 = __fmul_rn(0.5f, __fadd_rn(px, q.x)), av1 = __fmul_rn(0.5f, __fadd_rn(py, q.y)),
-                    av2 = __fmul_rn(0.5f, __fadd_rn(pz, q.z));
-        const float df0 = __fsub_rn(px, q.x), df1 = __fsub_rn(py, q.y), df2 = __fsub_rn(pz, q.z);
-        a[0] += 1.0;
-        a[1] += av0;
-        a[2] += av1;
-        a[3] += av2;
-        a[4] += __fmul_rn(av0, av2);                                           // -MM(3,4)
-        a[5] += __fmul_rn(av0, av1);                                           // -MM(3,5)
-        a[6] += __fmul_rn(av1, av2);                                           // -MM(4,5)
-        a[7] += __fadd_rn(__fmul_rn(av1, av1), __fmul_rn(av2, av2));           // MM(3,3)
-        a[8] += __fadd_rn(__fmul_rn(av0, av0), __fmul_rn(av1, av1));           // MM(4,4)
-        a[9] += __fadd_rn(__fmul_rn(av0, av0), __fmul_rn(av2, av2));           // MM(5,5)
-        a[10] += df0;
-        a[11] += df1;
-        a[12] += df2;
-        a[13] += __fsub_rn(__fmul_rn(av1, df2), __fmul_rn(av2, df1));
-        a[14] += __fsub_rn(__fmul_rn(av0, df1), __fmul_rn(av1, df0));
-        a[15] += __fsub_rn(__fmul_rn(av2, df0), __fmul_rn(av0, df2));
+        lum_terms(px, py, pz, q.x, q.y, q.z, a);
     }
     block_reduce_store<16>(a, partials);
 }
@@ -115,16 +88,11 @@ __global__ void __launch_bounds__(kBlock)
     for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const unsigned idx = (unsigned) keys[i];
         if (idx == kNoIdx || !info_owned(A, src[i])) continue;
+        const float4 p = src[i];
         float px, py, pz;
-        xform_f(A.Tf, src[i], px, py, pz);
+        xform_pcl(A.Tf, p.x, p.y, p.z, px, py, pz);
         const float4 q = tgt[idx];
-        const float av0 = __fmul_rn(0.5f, __fadd_rn(px, q.x)), av1 = __fmul_rn(0.5f, __fadd_rn(py, q.y)),
-                    av2 = __fmul_rn(0.5f, __fadd_rn(pz, q.z));
-        const float df0 = __fsub_rn(px, q.x), df1 = __fsub_rn(py, q.y), df2 = __fsub_rn(pz, q.z);
-        const double e0 = df0 - (A.D[0] + av2 * A.D[5] - av1 * A.D[4]);
-        const double e1 = df1 - (A.D[1] + av0 * A.D[4] - av2 * A.D[3]);
-        const double e2 = df2 - (A.D[2] + av1 * A.D[3] - av0 * A.D[5]);
-        a[0] += (double) (float) (e0 * e0 + e1 * e1 + e2 * e2);
+        a[0] += lum_residual(px, py, pz, q.x, q.y, q.z, A.D);
     }
     block_reduce_store<1>(a, partials);
 }
@@ -362,31 +330,8 @@ static int lum_from_current_keys(wm_ctx *ctx, const InfoArgs &args0, double info
     WM_HIP(ctx, hipGetLastError());
     double a[16];
     WM_TRY(reduce_partials(ctx, nb, 16, a, comm));
-    double MM[36] = {0}, MZ[6], MMinv[36], D[6];
-#define M_(r, c) MM[(r) * 6 + (c)]
-    M_(0, 4) = -a[2];
-    M_(0, 5) = a[3];
-    M_(1, 3) = -a[3];
-    M_(1, 4) = a[1];
-    M_(2, 3) = a[2];
-    M_(2, 5) = -a[1];
-    M_(3, 4) = -a[4];
-    M_(3, 5) = -a[5];
-    M_(4, 5) = -a[6];
-    M_(3, 3) = a[7];
-    M_(4, 4) = a[8];
-    M_(5, 5) = a[9];
-    M_(0, 0) = M_(1, 1) = M_(2, 2) = (double) (float) (int) a[0];
-    M_(4, 0) = M_(0, 4);
-    M_(5, 0) = M_(0, 5);
-    M_(3, 1) = M_(1, 3);
-    M_(4, 1) = M_(1, 4);
-    M_(3, 2) = M_(2, 3);
-    M_(5, 2) = M_(2, 5);
-    M_(4, 3) = M_(3, 4);
-    M_(5, 3) = M_(3, 5);
-    M_(5, 4) = M_(4, 5);
-#undef M_
+    double MM[36], MZ[6], MMinv[36], D[6];
+    lum_normal_matrix(a, MM);
     for (int k = 0; k < 6; ++k) MZ[k] = a[10 + k];
     inverse<6>(MM, MMinv);
     for (int r = 0; r < 6; ++r) {

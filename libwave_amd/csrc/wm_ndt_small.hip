@@ -18,6 +18,8 @@
 #include "wm_ndt_dev.hpp"
 #include "wm_ndt_ctl.hpp"
 #include "wm_gicp_dev.hpp"  // dd_add
+#include "wm_pair_terms.hpp"
+#include "wm_wave.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -78,49 +80,6 @@ struct NsShared {
     unsigned long long pass_cyc;
 };
 
-__device__ __forceinline__ bool ns_load(const unsigned char *base, unsigned i, unsigned stride, float &x, float &y, float &z) {
-    const float *p = reinterpret_cast<const float *>(base + (size_t) i * stride);
-    x = p[0], y = p[1], z = p[2];
-    return x - x == 0.f && y - y == 0.f && z - z == 0.f;  // finite
-}
-
-// exclusive scan of the counting sort's counts, four cells per thread at a time: run[c] = start[c] = first slot of cell
-// c (the counts were made by atomics, which live in L2: read there).  Every thread calls.
-__device__ __forceinline__ void ns_scan_counts(unsigned *run, unsigned *start, unsigned nc, NsShared &S) {
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    unsigned carry = 0;
-    for (unsigned c0 = 0; c0 < nc; c0 += 4u * kNsThreads) {
-        const unsigned c = c0 + 4u * tid;
-        unsigned v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = c + (unsigned) u < nc ? __hip_atomic_load(&run[c + (unsigned) u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const unsigned mine = v[0] + v[1] + v[2] + v[3];
-        unsigned incl = mine;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned up = __shfl_up(incl, m);
-            if ((int) lane >= m) incl += up;
-        }
-        if (lane == 63) S.scan[wave] = incl;
-        __syncthreads();
-        unsigned base = carry, all = 0;
-        for (unsigned w = 0; w < (unsigned) kNsWaves; ++w) {
-            if (w < wave) base += S.scan[w];
-            all += S.scan[w];
-        }
-        unsigned at = base + incl - mine;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (c + (unsigned) u < nc) {
-                run[c + (unsigned) u] = at;
-                start[c + (unsigned) u] = at;
-                at += v[u];
-            }
-        carry += all;
-        __syncthreads();
-    }
-}
-
 // pcl::VoxelGridCovariance::filter of the target (setInputTarget, ndt.cpp:55): S.dense / S.n_valid
 __device__ __attribute__((noinline)) void ns_build_model(NsShared &S) {
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -130,7 +89,7 @@ __device__ __attribute__((noinline)) void ns_build_model(NsShared &S) {
     unsigned cnt = 0;
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) {
+        if (load_point_finite(raw, i, stride, x, y, z)) {
             lo[0] = fminf(lo[0], x), lo[1] = fminf(lo[1], y), lo[2] = fminf(lo[2], z);
             hi[0] = fmaxf(hi[0], x), hi[1] = fmaxf(hi[1], y), hi[2] = fmaxf(hi[2], z);
             ++cnt;
@@ -206,16 +165,16 @@ __device__ __attribute__((noinline)) void ns_build_model(NsShared &S) {
     };
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) atomicAdd(&run[cell_of(x, y, z)], 1u);
+        if (load_point_finite(raw, i, stride, x, y, z)) atomicAdd(&run[cell_of(x, y, z)], 1u);
     }
     __syncthreads();
-    ns_scan_counts(run, start, nc, S);
+    block_scan_counts<kNsThreads>(run, start, nc, S.scan);
     if (tid == 0) start[nc] = cnt;
     __syncthreads();
     unsigned *order = S.pr.order;
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) order[atomicAdd(&run[cell_of(x, y, z)], 1u)] = i;
+        if (load_point_finite(raw, i, stride, x, y, z)) order[atomicAdd(&run[cell_of(x, y, z)], 1u)] = i;
     }
     __syncthreads();
     // one thread per occupied cell: n, sum p, sum p p^T.  The counting sort left a cell's points in no particular
@@ -228,7 +187,7 @@ __device__ __attribute__((noinline)) void ns_build_model(NsShared &S) {
         double sh[3] = {0, 0, 0}, sl[3] = {0, 0, 0}, ph[6] = {0, 0, 0, 0, 0, 0}, pl[6] = {0, 0, 0, 0, 0, 0};
         for (unsigned t = s0; t < s1; ++t) {
             float x, y, z;
-            (void) ns_load(raw, order[t], stride, x, y, z);
+            (void) load_point_finite(raw, order[t], stride, x, y, z);
             const double q[3] = {(double) x, (double) y, (double) z};
 #pragma unroll
             for (int a = 0; a < 3; ++a) dd_add(sh[a], sl[a], q[a]);
@@ -266,7 +225,7 @@ __device__ __attribute__((noinline)) void ns_sort_source(NsShared &S) {
     unsigned cnt = 0;
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) {
+        if (load_point_finite(raw, i, stride, x, y, z)) {
             lo[0] = fminf(lo[0], x), lo[1] = fminf(lo[1], y), lo[2] = fminf(lo[2], z);
             hi[0] = fmaxf(hi[0], x), hi[1] = fmaxf(hi[1], y), hi[2] = fmaxf(hi[2], z);
             ++cnt;
@@ -321,15 +280,15 @@ __device__ __attribute__((noinline)) void ns_sort_source(NsShared &S) {
     __syncthreads();
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) atomicAdd(&run[cell_of(x, y, z)], 1u);
+        if (load_point_finite(raw, i, stride, x, y, z)) atomicAdd(&run[cell_of(x, y, z)], 1u);
     }
     __syncthreads();
-    ns_scan_counts(run, start, nc, S);
+    block_scan_counts<kNsThreads>(run, start, nc, S.scan);
     if (tid == 0) start[nc] = cnt;
     __syncthreads();
     for (unsigned i = tid; i < n; i += kNsThreads) {
         float x, y, z;
-        if (ns_load(raw, i, stride, x, y, z)) order[atomicAdd(&run[cell_of(x, y, z)], 1u)] = i;
+        if (load_point_finite(raw, i, stride, x, y, z)) order[atomicAdd(&run[cell_of(x, y, z)], 1u)] = i;
     }
     __syncthreads();
     // a thread per cell puts its points in ascending index (insertion sort: a cell holds a few dozen), then writes them out
@@ -347,7 +306,7 @@ __device__ __attribute__((noinline)) void ns_sort_source(NsShared &S) {
         }
         for (unsigned a = s0; a < s1; ++a) {
             float x, y, z;
-            (void) ns_load(raw, order[a], stride, x, y, z);
+            (void) load_point_finite(raw, order[a], stride, x, y, z);
             spts[a] = make_float4(x, y, z, 1.f);
         }
     }

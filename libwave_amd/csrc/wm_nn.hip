@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
             prev = prev_e;
             tp = tp_e;
         }
-        xform(S.Tf, p_e, qx, qy, qz);
+        xform_pcl(S.Tf, p_e.x, p_e.y, p_e.z, qx, qy, qz);
         // sharded registration: only the rank owning this x-slab handles the point
         if (S.slab_on && !(qx >= S.slab_lo && qx < S.slab_hi)) mine = false;
     }
@@ -362,7 +362,7 @@ __global__ void __launch_bounds__(kBlock)
     const unsigned per = (m + gridDim.y - 1) / gridDim.y;
     const unsigned m0 = blockIdx.y * per, m1 = min(m0 + per, m);
     float qx = 0, qy = 0, qz = 0;
-    if (i < n) xform(st->Tf, src[i], qx, qy, qz);
+    if (i < n) xform_pcl(st->Tf, src[i].x, src[i].y, src[i].z, qx, qy, qz);
     const bool mine = !(st->slab_on && !(qx >= st->slab_lo && qx < st->slab_hi));
     unsigned long long best = make_key(thr_d2, kNoIdx);
     for (unsigned t0 = m0; t0 < m1; t0 += kBruteTile) {

@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 bool settled = false, owned = act;
                 float qx = 0.f, qy = 0.f, qz = 0.f, d2 = 0.f;
                 if (act) {
-                    xform(Tl, p[j], qx, qy, qz);
+                    xform_pcl(Tl, p[j].x, p[j].y, p[j].z, qx, qy, qz);
                     if (slab_on && !(qx >= slab_lo && qx < slab_hi)) owned = false;
                 }
                 if (owned && valid) {
@@ -493,7 +493,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
                 } else {
                     const float4 p1 = src[gi];
                     if (have_prev) gtp = match_pt[gi];
-                    xform(Tl, p1, gx, gy, gz);
+                    xform_pcl(Tl, p1.x, p1.y, p1.z, gx, gy, gz);
                 }
             }
             __syncthreads();
@@ -535,7 +535,7 @@ __global__ void __launch_bounds__(64 * kCertWaves) __attribute__((amdgpu_waves_p
             if (from_mem) {
                 const float4 p1 = src[i];
                 if (have_prev) tp = match_pt[i];
-                xform(Tl, p1, qx, qy, qz);
+                xform_pcl(Tl, p1.x, p1.y, p1.z, qx, qy, qz);
             }
             if (mine) {
                 r = r0_cells * h0;
@@ -741,7 +741,7 @@ __global__ void __launch_bounds__(kBlock)
     const float4 p = src[i], m = match_pt[i];
     const unsigned idx = __float_as_uint(m.w);
     float qx, qy, qz;
-    xform(st->Tf_search, p, qx, qy, qz);
+    xform_pcl(st->Tf_search, p.x, p.y, p.z, qx, qy, qz);
     keys[i] = idx == kNoIdx ? make_key(thr_d2, kNoIdx) : make_key(canon_d2(qx, qy, qz, m), idx);
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "wm_internal.hpp"
 #include "wm_icp_step.hpp"
+#include "wm_pair_terms.hpp"
 #include "wm_bins.hpp"
 #include "wm_wave.hpp"
 #include "wm_zigzag.hpp"
@@ -16,17 +17,6 @@ __device__ __forceinline__ unsigned long long make_key(float d2, unsigned idx) {
 __device__ __forceinline__ float canon_d2(float qx, float qy, float qz, const float4 &t) {
     const float dx = qx - t.x, dy = qy - t.y, dz = qz - t.z;
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-// PCL's float transform of a source point: ((m00*x + m01*y) + m02*z) + m03
-__device__ __forceinline__ void xform(const float *T, const float4 &p, float &x, float &y,
-                                      float &z) {
-    x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)),
-                            __fmul_rn(T[2], p.z)), T[3]);
-    y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)),
-                            __fmul_rn(T[6], p.z)), T[7]);
-    z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)),
-                            __fmul_rn(T[10], p.z)), T[11]);
 }
 
 // Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8).
@@ -964,59 +954,6 @@ __device__ __forceinline__ double add_wave_rows(const double (&rows)[kCertWaves]
 // n, sum p, sum q, sum q p^T, sum d2 | GN: n, sum p, A^T A, J^T r, sum d2; + the number of
 // points this rank handled).  Summing them here deletes a 40 MB stream and a launch per iteration.
 //
-// (the wave reduction by recursive halving: wm_wave.hpp)
-
-// this lane's terms of the iteration's sums (same arithmetic as k_icp_stats, wm_icp.hip)
-// a[17] counts the queries this rank handled; its fraction (units of 2^-24) counts those whose match
-// CHANGED in this search -- what the host decides by whether the next searches can be certified instead
-// (wm_icp_align).  Exact in a double, and never carrying into the integer part, because at most 2^23
-// queries report: beyond that size only every (IcpDevState::changed_mask + 1)-th does (changed_mask_for,
-// wm_icp_step.hpp) and the solve scales the count back up.
-constexpr double kChangedUnit = 1.0 / 16777216.0;
-template <int STATS>
-__device__ __forceinline__ void icp_terms(double (&a)[kAcc], bool mine, bool matched, float qx, float qy, float qz,
-                                          float bqx, float bqy, float bqz, float d2, bool changed = false) {
-#pragma unroll
-    for (int k = 0; k < kAcc; ++k) a[k] = 0.0;
-    if (mine) {
-        a[17] = changed ? 1.0 + kChangedUnit : 1.0;
-        if (matched) {
-            const double px = qx, py = qy, pz = qz, tx = bqx, ty = bqy, tz = bqz;
-            a[0] = 1.0;
-            a[1] = px;
-            a[2] = py;
-            a[3] = pz;
-            if constexpr (STATS == WM_ICP_SVD) {
-                a[4] = tx;
-                a[5] = ty;
-                a[6] = tz;
-                a[7] = tx * px;
-                a[8] = tx * py;
-                a[9] = tx * pz;
-                a[10] = ty * px;
-                a[11] = ty * py;
-                a[12] = ty * pz;
-                a[13] = tz * px;
-                a[14] = tz * py;
-                a[15] = tz * pz;
-            } else {
-                const double rx = px - tx, ry = py - ty, rz = pz - tz;
-                a[4] = py * py + pz * pz;
-                a[5] = -px * py;
-                a[6] = -px * pz;
-                a[7] = px * px + pz * pz;
-                a[8] = -py * pz;
-                a[9] = px * px + py * py;
-                a[10] = rx;
-                a[11] = ry;
-                a[12] = rz;
-                a[13] = py * rz - pz * ry;
-                a[14] = pz * rx - px * rz;
-                a[15] = px * ry - py * rx;
-            }
-            a[16] = (double) d2;
-        }
-    }
-}
+// (a lane's terms: icp_terms, wm_pair_terms.hpp; the wave reduction by recursive halving: wm_wave.hpp)
 
 }  // namespace wm

@@ -13,6 +13,7 @@
 #include "wm_icp_step.hpp"
 #include "wm_bins.hpp"
 #include "wm_gicp_dev.hpp"
+#include "wm_pair_terms.hpp"
 
 #include <string.h>
 
@@ -178,9 +179,8 @@ __global__ void __launch_bounds__(kBlock)
             if ((int) (unsigned) (key >> 32) > rej_thr) continue;  // rejected
             // the source point under the pose the search used: the search kernels' float arithmetic
             const float4 p4 = pv[u];
-            const float fx = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p4.x), __fmul_rn(T[1], p4.y)), __fmul_rn(T[2], p4.z)), T[3]);
-            const float fy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p4.x), __fmul_rn(T[5], p4.y)), __fmul_rn(T[6], p4.z)), T[7]);
-            const float fz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p4.x), __fmul_rn(T[9], p4.y)), __fmul_rn(T[10], p4.z)), T[11]);
+            float fx, fy, fz;
+            xform_pcl(T, p4.x, p4.y, p4.z, fx, fy, fz);
             a[kGnN] += 1.0;
             a[kGnSd2] += (double) __uint_as_float((unsigned) (key >> 32));  // the search's own d2, as the other modes' MSE
             const float4 n4 = nv[u];

@@ -15,6 +15,7 @@
 // that launches all of it is icp_run_loop's.  Every kernel here returns on st->done, so that behind the last executed
 // iteration the record on the device is still that iteration's.
 #include "wm_internal.hpp"
+#include "wm_wave.hpp"
 
 #include <float.h>
 #include <math.h>
@@ -134,12 +135,7 @@ __global__ void __launch_bounds__(kBlock)
     }
     // exclusive sum of `mine` over the workgroup's threads
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off);
-        if (lane >= (unsigned) off) incl += t;
-    }
+    const unsigned incl = wave_incl_scan(mine, lane);
     if (lane == 63u) s_wave[wave] = incl;
     if (threadIdx.x == 0) s_bin = 0xFFFFFFFFu;
     __syncthreads();

@@ -22,6 +22,7 @@
 
 #include "wm_internal.hpp"
 #include "wm_xchg.hpp"
+#include "wm_wave.hpp"
 
 #include <rccl/rccl.h>
 
@@ -312,12 +313,7 @@ __global__ void __launch_bounds__(kPlanThreads)
         const unsigned v = s_hist[plan_word(t * (kPer / 2) + w)];
         mine += (v & 0xFFFFu) + (v >> 16);
     }
-    unsigned incl = mine;  // inclusive scan across the workgroup: in the wave, then over the waves' totals
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned up = (unsigned) __shfl_up((int) incl, off);
-        if ((int) (t & 63u) >= off) incl += up;
-    }
+    const unsigned incl = wave_incl_scan(mine, t & 63u);  // inclusive scan across the workgroup: in the wave, then over the waves' totals
     if ((t & 63u) == 63u) s_wave[t >> 6] = incl;
     __syncthreads();
     unsigned before = incl - mine, total = 0;
@@ -429,12 +425,7 @@ __device__ unsigned scan_in_place(unsigned *__restrict__ cnt, unsigned n, unsign
     const unsigned b0 = min(t * per, n), b1 = min(b0 + per, n);
     unsigned mine = 0;
     for (unsigned b = b0; b < b1; ++b) mine += cnt[b];
-    unsigned incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned up = (unsigned) __shfl_up((int) incl, off);
-        if ((int) (t & 63u) >= off) incl += up;
-    }
+    const unsigned incl = wave_incl_scan(mine, t & 63u);
     __syncthreads();  // (s_wave may still be read from an earlier call)
     if ((t & 63u) == 63u) s_wave[t >> 6] = incl;
     __syncthreads();

@@ -12,28 +12,31 @@
 //   + the estimator whose result estimateInfo() keeps  icp.cpp:135-142 -> estimateLUMold,
 //                                                      icp_pcl_functions.cpp:51-179
 // -- and a launch carries one workgroup per queued pair, so 256 pairs fill the 256 CUs and nothing
-// crosses a launch boundary:
-//   0. the source is put in cell order (bitonic sort of unique keys in LDS; a packed copy in HBM
+// crosses a launch boundary.  k_icp_small is an outline of these steps, each a function below:
+//   0. sm_order_source: the source is put in cell order (bitonic sort of unique keys in LDS; a packed copy in HBM
 //      scratch), so that neighbouring lanes search neighbouring cells;
-//   1. the target cloud is counting-sorted by cell INTO LDS (x, y, z floats + a 16-bit original
+//   1. sm_sort_target: the target cloud is counting-sorted by cell INTO LDS (x, y, z floats + a 16-bit original
 //      index per point: 14 B x 10 000 points = 140 kB of the CU's 160 KB; 8 192 cells, 16-bit starts;
 //      the grid covers the CORE of the cloud, outliers are clamped into its border cells) --
 //      k_icp_small<true>; targets of up to 65 535 points keep that cell-sorted copy in HBM scratch
 //      (L2 / Infinity Cache resident; only the cell starts live in LDS) -- k_icp_small<false>;
-//   2. every iteration chunks of 64 queries go to whichever wavefront is free: PCL's float transform,
-//      an exact 1-NN search over the cell rows overlapping a certified ball (radius = distance to the
-//      previous iteration's match under the new pose, so one scan certifies), the same 64-bit
+//   2. sm_iteration: every iteration chunks of 64 queries go to whichever wavefront is free: PCL's float transform
+//      (xform_pcl), an exact 1-NN search over the cell rows overlapping a certified ball (sm_seeded_search: radius =
+//      distance to the previous iteration's match under the new pose, so one scan certifies), the same 64-bit
 //      (d2 bits, index) arg-min key as wm_nn.hip -- hence the same correspondences, bit for bit --
-//      and the iteration's 17 sums in double, reduced per chunk so that the result does not depend
-//      on which wavefront took which chunk;
-//   3. a fixed-order sum of the chunk rows, then lane 0 runs the very solve + stopping rules of the
+//      and the iteration's 17 sums in double (icp_pair_terms: the terms k_icp_stats and the fused search sum),
+//      reduced per chunk so that the result does not depend on which wavefront took which chunk;
+//   3. a fixed-order sum of the chunk rows, then sm_solve: lane 0 runs the very solve + stopping rules of the
 //      big path (icp_apply_stats, wm_icp_step.hpp) on a state that lives in LDS;
-//   4. after the last iteration the LUMold normal equations and residual, same arithmetic as
-//      wm_info.hip.
+//   4. sm_lumold: after the last iteration the LUMold normal equations and residual (lum_terms, lum_normal_matrix,
+//      lum_residual: the definitions wm_info.hip runs), then sm_write_out.
+// The per-pair formulas are wm_pair_terms.hpp's, the scans wm_wave.hpp's: one definition each, for this path and the
+// one-pair path alike (tests/test_small_pinned_gpu.py pins the returned bits).
 // Latency of ONE registration is worse than wm_icp_align's (one CU instead of a hundred); this path
 // is for queues of pairs.  The voxel-filtered branches of match() are built on top of it in
 // wm_batch.hip (small_run below is what they call, scale by scale).
 #include "wm_icp_step.hpp"
+#include "wm_pair_terms.hpp"
 #include "wm_stage.hpp"
 #include "wm_wave.hpp"
 
@@ -149,13 +152,6 @@ __device__ __forceinline__ float sm_d2(float qx, float qy, float qz, float tx, f
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;  // (as canon_d2, wm_nn_scan.hpp)
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
-// PCL's float transform of a source point: ((m00*x + m01*y) + m02*z) + m03
-__device__ __forceinline__ void sm_xform(const float (&T)[12], float px, float py, float pz, float &x,
-                                         float &y, float &z) {
-    x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], px), __fmul_rn(T[1], py)), __fmul_rn(T[2], pz)), T[3]);
-    y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], px), __fmul_rn(T[5], py)), __fmul_rn(T[6], pz)), T[7]);
-    z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], px), __fmul_rn(T[9], py)), __fmul_rn(T[10], pz)), T[11]);
-}
 
 struct SmGrid {  // (wave-uniform: lives in scalar registers)
     float ox, oy, oz, inv_h, h;
@@ -235,15 +231,6 @@ __device__ __forceinline__ void sm_block_sum(double (&a)[N], LDS &L, unsigned ti
     __syncthreads();
 }
 
-__device__ __forceinline__ bool sm_load_point(const unsigned char *base, unsigned i, unsigned stride, float &x,
-                                              float &y, float &z) {
-    const float *p = reinterpret_cast<const float *>(base + (size_t) i * stride);
-    x = p[0];
-    y = p[1];
-    z = p[2];
-    return isfinite(x) && isfinite(y) && isfinite(z);  // (non-finite points are dropped, as k_pack does)
-}
-
 // The grid of a cloud: the finest cubic cells, at most `max_cells` of them, over the CORE of its finite
 // points -- their bounding box cut back to mean +- 2.5 standard deviations per axis.  Points outside
 // land in the border cells (cell coordinates are clamped, for points and for search boxes alike, so
@@ -259,7 +246,7 @@ __device__ __forceinline__ SmGrid sm_fit_grid(LDS &L, const unsigned char *pts, 
     unsigned cnt = 0;
     for (unsigned i = tid; i < n; i += kSmThreads) {
         float x, y, z;
-        if (sm_load_point(pts, i, stride, x, y, z)) {
+        if (load_point_finite(pts, i, stride, x, y, z)) {
             lo0 = fminf(lo0, x), lo1 = fminf(lo1, y), lo2 = fminf(lo2, z);
             hi0 = fmaxf(hi0, x), hi1 = fmaxf(hi1, y), hi2 = fmaxf(hi2, z);
             m1[0] += x, m1[1] += y, m1[2] += z;
@@ -381,52 +368,33 @@ __device__ __forceinline__ unsigned sm_cell_of(const SmGrid &g, float x, float y
                        sm_cell1(x, g.ox, g.inv_h, g.nx));
 }
 
-template <bool INLDS>
-__global__ void __launch_bounds__(kSmThreads)
-    k_icp_small(const SmallPair *__restrict__ pairs, SmallParams P, IcpDevState st0, SmallOut *__restrict__ out) {
-    using LDS = typename std::conditional<INLDS, SmallLds, SmallLdsH>::type;
-    using TG = typename std::conditional<INLDS, SmTgtLds, SmTgtHbm>::type;
+// ---- 0. the source in cell order (of a grid over its own bounding box): neighbouring lanes then
+// search neighbouring cells -- the same LDS rows (broadcast reads instead of bank conflicts) for a
+// similar number of trips.  The order is a bitonic sort, in the LDS the target will occupy, of the
+// unique keys (cell << 14 or 15 | index): deterministic, so the sums of a pair do not depend on timing.
+// The sorted copy (x, y, z, index bits) lives in HBM scratch; clouds beyond 16 384 (32 768) points keep
+// the caller's order, and so do sources that come out of a voxel filter (leaf order IS a cell order)
+// (packed all the same: the iterations read one layout).  -> the queries per iteration
+template <bool INLDS, class LDS>
+__device__ __forceinline__ unsigned sm_order_source(LDS &L, const SmallPair &pr, unsigned stride, unsigned tid) {
     constexpr unsigned kSortMax = 1u << kSmSortBits<INLDS>;
-    constexpr int kCells = INLDS ? kSmCells : kSmCellsHbm;
-    __shared__ LDS L;
-    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const SmallPair pr = pairs[blockIdx.x];
-    const unsigned long long cyc_begin = clock64();
-    constexpr unsigned kMaxT = INLDS ? (unsigned) kSmMaxTgt : (unsigned) kSmMaxTgtHbm;
-    const unsigned n_tgt = pr.n_tgt < kMaxT ? pr.n_tgt : kMaxT;  // (host checked)
-
-    if (tid == 0) {
-        L.st = st0;
-        L.st.prev_mse = pr.prev_mse0;
-        L.ticket = kSmWaves;
-    }
-
-    // ---- 0. the source in cell order (of a grid over its own bounding box): neighbouring lanes then
-    // search neighbouring cells -- the same LDS rows (broadcast reads instead of bank conflicts) for a
-    // similar number of trips.  The order is a bitonic sort, in the LDS the target will occupy, of the
-    // unique keys (cell << 14 or 15 | index): deterministic, so the sums of a pair do not depend on timing.
-    // The sorted copy (x, y, z, index bits) lives in HBM scratch; clouds beyond 16 384 (32 768) points keep
-    // the caller's order, and so do sources that come out of a voxel filter (leaf order IS a cell order)
-    // (packed all the same: the iterations read one layout).
-    unsigned n_q = pr.n_src;  // queries per iteration
+    unsigned n_q = pr.n_src;
     if (pr.n_src > kSortMax || pr.presorted) {
         for (unsigned i = tid; i < pr.n_src; i += kSmThreads) {
             float x, y, z;
-            if (!sm_load_point(pr.src, i, P.stride, x, y, z)) x = y = z = __builtin_nanf("");
+            if (!load_point_finite(pr.src, i, stride, x, y, z)) x = y = z = __builtin_nanf("");
             pr.sorted[i] = make_float4(x, y, z, __uint_as_float(i));
         }
-        __threadfence_block();
-        __syncthreads();
     } else {
         unsigned n_fin;
-        const SmGrid gs = sm_fit_grid(L, pr.src, pr.n_src, P.stride, kSmCells, tid, n_fin);
+        const SmGrid gs = sm_fit_grid(L, pr.src, pr.n_src, stride, kSmCells, tid, n_fin);
         unsigned N = 2048;
         while (N < pr.n_src) N <<= 1;
         unsigned *K = sm_sort_region(L);
         for (unsigned i = tid; i < N; i += kSmThreads) {
             unsigned key = ~0u;
             float x, y, z;
-            if (i < pr.n_src && sm_load_point(pr.src, i, P.stride, x, y, z)) key = (sm_cell_of(gs, x, y, z) << kSmSortBits<INLDS>) | i;
+            if (i < pr.n_src && load_point_finite(pr.src, i, stride, x, y, z)) key = (sm_cell_of(gs, x, y, z) << kSmSortBits<INLDS>) | i;
             K[i] = key;
         }
         for (unsigned k = 2; k <= N; k <<= 1)
@@ -445,414 +413,384 @@ __global__ void __launch_bounds__(kSmThreads)
         for (unsigned q = tid; q < n_fin; q += kSmThreads) {
             const unsigned i = K[q] & (kSortMax - 1u);
             float x, y, z;
-            (void) sm_load_point(pr.src, i, P.stride, x, y, z);
+            (void) load_point_finite(pr.src, i, stride, x, y, z);
             pr.sorted[q] = make_float4(x, y, z, __uint_as_float(i));
         }
         n_q = n_fin;
-        __threadfence_block();
-        __syncthreads();
     }
+    __threadfence_block();
+    __syncthreads();
+    return n_q;
+}
 
-    // ---- 1. the target cell-sorted -- into LDS, or into the pair's HBM scratch when it is too large for that:
-    // bounding box -> grid -> counting sort by cell
-    unsigned n_tgt_fin;
-    const SmGrid g = sm_fit_grid(L, pr.tgt, n_tgt, P.stride, kCells, tid, n_tgt_fin);
-    TG tg;
-    if constexpr (INLDS) {
-        tg.L = &L;
-        for (unsigned c = tid; c < (kSmCells + 8) / 2; c += kSmThreads) reinterpret_cast<unsigned *>(L.cstart)[c] = 0u;
-        __syncthreads();
-        {
-            // count: two 16-bit counters per LDS word; the returned old value is the point's rank in its cell
-            unsigned cr[kSmPer];
-            unsigned *cw = reinterpret_cast<unsigned *>(L.cstart);
+// ---- 1. the target cell-sorted -- into LDS, or into the pair's HBM scratch when it is too large for that:
+// bounding box -> grid (sm_fit_grid: g, n_fin finite points) -> counting sort by cell.  Both forms count with an
+// atomic whose old value is the point's rank in its cell, scan the counts in place (a lane's consecutive cells, then
+// sm_lanes_before) and end with four far sentinels behind the last point (see sm_search); they differ in where the
+// counters and the ranks live.
+
+// the sum of `mine` over the lanes of the workgroup before this one: a scan in the wave, then the waves' totals
+template <class LDS>
+__device__ __forceinline__ unsigned sm_lanes_before(LDS &L, unsigned mine, unsigned tid) {
+    const unsigned lane = tid & 63u, wave = tid >> 6;
+    const unsigned incl = wave_incl_scan(mine, lane);
+    if (lane == 63) L.wsum[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - mine;
+    for (unsigned w = 0; w < wave; ++w) run += L.wsum[w];
+    return run;
+}
+
+// into LDS: two 16-bit counters per LDS word, (cell << 16 | rank) of a lane's ten points in registers
+__device__ __forceinline__ SmTgtLds sm_sort_target(SmallLds &L, const SmallPair &pr, const SmGrid &g, unsigned n_tgt, unsigned n_fin,
+                                                   unsigned stride, unsigned tid) {
+    for (unsigned c = tid; c < (kSmCells + 8) / 2; c += kSmThreads) reinterpret_cast<unsigned *>(L.cstart)[c] = 0u;
+    __syncthreads();
+    unsigned cr[kSmPer];
+    unsigned *cw = reinterpret_cast<unsigned *>(L.cstart);
 #pragma unroll
-            for (int k = 0; k < kSmPer; ++k) {
-                const unsigned i = tid + (unsigned) k * kSmThreads;
-                cr[k] = ~0u;
-                float x, y, z;
-                if (i < n_tgt && sm_load_point(pr.tgt, i, P.stride, x, y, z)) {
-                    const unsigned c = sm_cell_of(g, x, y, z);
-                    const unsigned sh = (c & 1u) * 16u;
-                    const unsigned old = atomicAdd(&cw[c >> 1], 1u << sh);
-                    cr[k] = (c << 16) | ((old >> sh) & 0xFFFFu);
-                }
-            }
-            __syncthreads();
-            // exclusive scan of the 8 192 counts, in place (8 per lane)
-            constexpr int E = kSmCells / kSmThreads;
-            unsigned v[E], s = 0;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                v[e] = L.cstart[E * tid + e];
-                s += v[e];
-            }
-            unsigned incl = s;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned t = __shfl_up(incl, off);
-                if (lane >= (unsigned) off) incl += t;
-            }
-            if (lane == 63) L.wsum[wave] = incl;
-            __syncthreads();
-            unsigned run = incl - s;
-            for (unsigned w = 0; w < wave; ++w) run += L.wsum[w];
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                L.cstart[E * tid + e] = (unsigned short) run;
-                run += v[e];
-            }
-            if (tid == kSmThreads - 1) L.cstart[kSmCells] = (unsigned short) run;
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < kSmPer; ++k) {
-                if (cr[k] == ~0u) continue;
-                const unsigned i = tid + (unsigned) k * kSmThreads;
-                float x, y, z;
-                (void) sm_load_point(pr.tgt, i, P.stride, x, y, z);
-                const unsigned slot = (unsigned) L.cstart[cr[k] >> 16] + (cr[k] & 0xFFFFu);
-                L.xyz[3u * slot] = x, L.xyz[3u * slot + 1u] = y, L.xyz[3u * slot + 2u] = z;
-                L.idx[slot] = (unsigned short) i;
-            }
-            if (tid < 4u) {  // far sentinels behind the last point (see sm_search)
-                const unsigned slot = n_tgt_fin + tid;
-                L.xyz[3u * slot] = L.xyz[3u * slot + 1u] = L.xyz[3u * slot + 2u] = INFINITY;
-                L.idx[slot] = 0xFFFFu;
-            }
-            __syncthreads();
+    for (int k = 0; k < kSmPer; ++k) {
+        const unsigned i = tid + (unsigned) k * kSmThreads;
+        cr[k] = ~0u;
+        float x, y, z;
+        if (i < n_tgt && load_point_finite(pr.tgt, i, stride, x, y, z)) {
+            const unsigned c = sm_cell_of(g, x, y, z);
+            const unsigned sh = (c & 1u) * 16u;
+            const unsigned old = atomicAdd(&cw[c >> 1], 1u << sh);
+            cr[k] = (c << 16) | ((old >> sh) & 0xFFFFu);
         }
-    } else {
-        unsigned *cs = pr.tcs;
-        for (unsigned c = tid; c < (unsigned) kCells + 8u; c += kSmThreads) cs[c] = 0u;
-        __threadfence_block();
-        __syncthreads();
-        // count: the atomic's old value is the point's rank in its cell; (cell << 16 | rank) kept in scratch
-        for (unsigned i = tid; i < n_tgt; i += kSmThreads) {
-            unsigned cr = ~0u;
-            float x, y, z;
-            if (sm_load_point(pr.tgt, i, P.stride, x, y, z)) {
-                const unsigned c = sm_cell_of(g, x, y, z);
-                cr = (c << 16) | (atomicAdd(&cs[c], 1u) & 0xFFFFu);
-            }
-            pr.trank[i] = cr;
-        }
-        __threadfence_block();
-        __syncthreads();
-        // exclusive scan of the 64 512 counts, in place (63 consecutive per lane)
-        constexpr int E = kSmCellsHbm / kSmThreads;
-        unsigned sum = 0;
-        for (int e = 0; e < E; ++e) sum += ((const __attribute__((address_space(1))) unsigned *) cs)[E * tid + e];
-        unsigned incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned t = __shfl_up(incl, off);
-            if (lane >= (unsigned) off) incl += t;
-        }
-        if (lane == 63) L.wsum[wave] = incl;
-        __syncthreads();
-        unsigned run = incl - sum;
-        for (unsigned w = 0; w < wave; ++w) run += L.wsum[w];
-        for (int e = 0; e < E; ++e) {
-            const unsigned v = cs[E * tid + e];
-            cs[E * tid + e] = run;
-            run += v;
-        }
-        if (tid == kSmThreads - 1) cs[kCells] = run;
-        __threadfence_block();
-        __syncthreads();
-        for (unsigned i = tid; i < n_tgt; i += kSmThreads) {
-            const unsigned cr = pr.trank[i];
-            if (cr == ~0u) continue;
-            float x, y, z;
-            (void) sm_load_point(pr.tgt, i, P.stride, x, y, z);
-            const unsigned slot = cs[cr >> 16] + (cr & 0xFFFFu);
-            pr.txyz[3u * slot] = x, pr.txyz[3u * slot + 1u] = y, pr.txyz[3u * slot + 2u] = z;
-            pr.tidx[slot] = (unsigned short) i;
-        }
-        if (tid < 4u) {  // far sentinels behind the last point (see sm_search)
-            const unsigned slot = n_tgt_fin + tid;
-            pr.txyz[3u * slot] = pr.txyz[3u * slot + 1u] = pr.txyz[3u * slot + 2u] = INFINITY;
-            pr.tidx[slot] = 0xFFFFu;
-        }
-        __threadfence_block();
-        __syncthreads();
-        tg.xyz = (const __attribute__((address_space(1))) float *) pr.txyz;
-        tg.idxp = (const __attribute__((address_space(1))) unsigned short *) pr.tidx;
-        // the 64 513 cell starts fit 16 bits (<= 65 535 points): into the LDS the source's sort has left
-        unsigned short *csl = reinterpret_cast<unsigned short *>(L.sortbuf);
-        for (unsigned c = tid; c <= (unsigned) kCells; c += kSmThreads) csl[c] = (unsigned short) cs[c];
-        __syncthreads();
-        tg.csl = csl;
     }
-    const float rmax = sqrtf(P.thr_d2) * 1.0001f + 1e-6f;
+    __syncthreads();
+    // exclusive scan of the 8 192 counts, in place (8 per lane)
+    constexpr int E = kSmCells / kSmThreads;
+    unsigned v[E], s = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        v[e] = L.cstart[E * tid + e];
+        s += v[e];
+    }
+    unsigned run = sm_lanes_before(L, s, tid);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        L.cstart[E * tid + e] = (unsigned short) run;
+        run += v[e];
+    }
+    if (tid == kSmThreads - 1) L.cstart[kSmCells] = (unsigned short) run;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSmPer; ++k) {
+        if (cr[k] == ~0u) continue;
+        const unsigned i = tid + (unsigned) k * kSmThreads;
+        float x, y, z;
+        (void) load_point_finite(pr.tgt, i, stride, x, y, z);
+        const unsigned slot = (unsigned) L.cstart[cr[k] >> 16] + (cr[k] & 0xFFFFu);
+        L.xyz[3u * slot] = x, L.xyz[3u * slot + 1u] = y, L.xyz[3u * slot + 2u] = z;
+        L.idx[slot] = (unsigned short) i;
+    }
+    if (tid < 4u) {
+        const unsigned slot = n_fin + tid;
+        L.xyz[3u * slot] = L.xyz[3u * slot + 1u] = L.xyz[3u * slot + 2u] = INFINITY;
+        L.idx[slot] = 0xFFFFu;
+    }
+    __syncthreads();
+    SmTgtLds tg;
+    tg.L = &L;
+    return tg;
+}
+
+// into HBM scratch: 32-bit counters in pr.tcs, (cell << 16 | rank) of every point in pr.trank
+__device__ __forceinline__ SmTgtHbm sm_sort_target(SmallLdsH &L, const SmallPair &pr, const SmGrid &g, unsigned n_tgt, unsigned n_fin,
+                                                   unsigned stride, unsigned tid) {
+    constexpr int kCells = kSmCellsHbm;
+    unsigned *cs = pr.tcs;
+    for (unsigned c = tid; c < (unsigned) kCells + 8u; c += kSmThreads) cs[c] = 0u;
+    __threadfence_block();
+    __syncthreads();
+    for (unsigned i = tid; i < n_tgt; i += kSmThreads) {
+        unsigned cr = ~0u;
+        float x, y, z;
+        if (load_point_finite(pr.tgt, i, stride, x, y, z)) {
+            const unsigned c = sm_cell_of(g, x, y, z);
+            cr = (c << 16) | (atomicAdd(&cs[c], 1u) & 0xFFFFu);
+        }
+        pr.trank[i] = cr;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // exclusive scan of the 64 512 counts, in place (63 consecutive per lane)
+    constexpr int E = kCells / kSmThreads;
+    unsigned sum = 0;
+    for (int e = 0; e < E; ++e) sum += ((const __attribute__((address_space(1))) unsigned *) cs)[E * tid + e];
+    unsigned run = sm_lanes_before(L, sum, tid);
+    for (int e = 0; e < E; ++e) {
+        const unsigned v = cs[E * tid + e];
+        cs[E * tid + e] = run;
+        run += v;
+    }
+    if (tid == kSmThreads - 1) cs[kCells] = run;
+    __threadfence_block();
+    __syncthreads();
+    for (unsigned i = tid; i < n_tgt; i += kSmThreads) {
+        const unsigned cr = pr.trank[i];
+        if (cr == ~0u) continue;
+        float x, y, z;
+        (void) load_point_finite(pr.tgt, i, stride, x, y, z);
+        const unsigned slot = cs[cr >> 16] + (cr & 0xFFFFu);
+        pr.txyz[3u * slot] = x, pr.txyz[3u * slot + 1u] = y, pr.txyz[3u * slot + 2u] = z;
+        pr.tidx[slot] = (unsigned short) i;
+    }
+    if (tid < 4u) {
+        const unsigned slot = n_fin + tid;
+        pr.txyz[3u * slot] = pr.txyz[3u * slot + 1u] = pr.txyz[3u * slot + 2u] = INFINITY;
+        pr.tidx[slot] = 0xFFFFu;
+    }
+    __threadfence_block();
+    __syncthreads();
+    SmTgtHbm tg;
+    tg.xyz = (const __attribute__((address_space(1))) float *) pr.txyz;
+    tg.idxp = (const __attribute__((address_space(1))) unsigned short *) pr.tidx;
+    // the 64 513 cell starts fit 16 bits (<= 65 535 points): into the LDS the source's sort has left
+    unsigned short *csl = reinterpret_cast<unsigned short *>(L.sortbuf);
+    for (unsigned c = tid; c <= (unsigned) kCells; c += kSmThreads) csl[c] = (unsigned short) cs[c];
+    __syncthreads();
+    tg.csl = csl;
+    return tg;
+}
+
+// ---- 2. the search of one query, as the iterations and the LUMold pass run it: the exact nearest neighbour of q
+// within the gate thr_d2 (rmax: the gate's radius, a little wide).  `seed` = the slot of the query's last match
+// (0xFFFF none), read when the state has a previous iteration.  The first ball:
+//   no previous iteration                       r0 (half a cell)
+//   the seed's distance under the NEW pose      when the seed is inside the gate: it is a real candidate, so its
+//                                               distance bounds the new neighbour's and one scan of that ball certifies
+//   rmax                                        no seed, or a seed outside the gate
+struct SmMatch {
+    unsigned long long key;  // (d2 bits, caller's index) -- kNoIdx: nothing within the gate
+    unsigned slot;           // its slot
+    bool matched;
+};
+template <class TG>
+__device__ __forceinline__ SmMatch sm_seeded_search(const TG &tg, const SmGrid &g, float qx, float qy, float qz, float thr_d2,
+                                                    float rmax, float r0, bool have_prev, unsigned seed) {
+    SmMatch m;
+    m.key = sm_key(thr_d2, kNoIdx);
+    m.slot = 0xFFFFu;
+    float r = have_prev ? rmax : r0;
+    if (have_prev && seed != 0xFFFFu) {
+        const float d2b = sm_d2(qx, qy, qz, tg.c(seed, 0), tg.c(seed, 1), tg.c(seed, 2));
+        if (d2b <= thr_d2) {
+            m.key = sm_key(d2b, tg.idx(seed));
+            m.slot = seed;
+            r = fmaxf(sqrtf(d2b) * 1.0001f + 1e-6f, 0.05f * g.h);
+        }
+    }
+    sm_search(tg, g, qx, qy, qz, fminf(r, rmax), rmax, m.key, m.slot);
+    m.matched = (unsigned) m.key != kNoIdx;
+    return m;
+}
+
+// one query of an iteration: PCL's float transform, the search, the new seed, and its terms of the iteration's sums
+// (icp_pair_terms, wm_pair_terms.hpp: what k_icp_stats adds) added to a
+template <class TG>
+__device__ __forceinline__ void sm_query_terms(const TG &tg, const SmGrid &g, const SmallPair &pr, const SmallParams &P,
+                                               const float (&Tf)[12], bool have_prev, int mode, float rmax, unsigned q,
+                                               const SmQuery &c, double (&a)[kAcc]) {
+    if (!(c.x == c.x)) return;  // (a non-finite point of a cloud too large to be sorted)
+    float qx, qy, qz;
+    xform_pcl(Tf, c.x, c.y, c.z, qx, qy, qz);
+    const SmMatch m = sm_seeded_search(tg, g, qx, qy, qz, P.thr_d2, rmax, P.r0_cells * g.h, have_prev, c.seed);
+    pr.seed[q] = (unsigned short) (m.matched ? m.slot : 0xFFFFu);
+    a[17] += 1.0;
+    if (!m.matched) return;
+    const float tx = tg.c(m.slot, 0), ty = tg.c(m.slot, 1), tz = tg.c(m.slot, 2), d2 = __uint_as_float((unsigned) (m.key >> 32));
+    auto add = [&](int k, double term) { a[k] += term; };
+    if (mode == WM_ICP_SVD) icp_pair_terms<WM_ICP_SVD>(qx, qy, qz, tx, ty, tz, d2, add);
+    else icp_pair_terms<WM_ICP_GN6>(qx, qy, qz, tx, ty, tz, d2, add);
+}
+
+struct SmClock {  // developer: shader-clock cycles of the last iteration's query loop / reduction / solve, and of the set-up
+    unsigned long long loop, red, solve, setup;
+};
+
+// ---- 2./3. one iteration's sums -> L.sum; returns the clock at its end.
+// Chunks of 64 consecutive (cell-ordered) queries go to whichever wavefront is free: the first
+// sixteen by wave number, the rest by a ticket in LDS -- static shares left the slowest wave
+// 45 % behind the first.  A chunk's sums are reduced inside its wavefront (recursive halving,
+// wm_wave.hpp) into a row of their own, so which wave took which chunk cannot change a bit of
+// the result; the next chunk's ticket is drawn, and its loads issued, before this chunk's search.
+// Then the rows are added in a fixed order: 16 interleaved partial sums, then those.
+template <class LDS, class TG>
+__device__ __forceinline__ unsigned long long sm_iteration(LDS &L, const TG &tg, const SmGrid &g, const SmallPair &pr,
+                                                           const SmallParams &P, unsigned n_q, float rmax, unsigned tid, SmClock &ck) {
+    const unsigned lane = tid & 63u, wave = tid >> 6;
     const unsigned nchunks = (n_q + 63u) / 64u;
-    const unsigned long long cyc_setup = clock64() - cyc_begin;
-    unsigned long long cyc_loop = 0, cyc_red = 0, cyc_solve = 0;
+    float Tf[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tf[k] = L.st.Tf[k];
+    const bool have_prev = L.st.have_prev != 0;
+    const int mode = L.st.mode;
+    const unsigned long long t0 = clock64();
+    unsigned c = wave;
+    bool has = c < nchunks;
+    unsigned q = c * 64u + lane;
+    SmQuery cur = {0.f, 0.f, 0.f, 0xFFFFu};
+    if (has && q < n_q) cur = sm_fetch(pr, q);
+    while (has) {
+        unsigned cn = 0;
+        if (lane == 0) cn = atomicAdd(&L.ticket, 1u);
+        cn = (unsigned) __builtin_amdgcn_readfirstlane((int) cn);
+        const bool hn = cn < nchunks;
+        const unsigned qn = cn * 64u + lane;
+        SmQuery nxt = cur;
+        if (hn && qn < n_q) nxt = sm_fetch(pr, qn);
+        double a[kAcc];
+#pragma unroll
+        for (int k = 0; k < kAcc; ++k) a[k] = 0.0;
+        if (q < n_q) sm_query_terms(tg, g, pr, P, Tf, have_prev, mode, rmax, q, cur, a);
+        acc_halve<kAcc, 32>(a, lane);
+        const int comp = acc_comp_of_lane(lane);
+        if (comp >= 0) pr.csum[(size_t) c * kAcc + comp] = a[0];
+        c = cn, q = qn, cur = nxt, has = hn;
+    }
+    const unsigned long long t1 = clock64();
+    __threadfence_block();
+    __syncthreads();
+    if (tid < (unsigned) (kSmWaves * kAcc)) {
+        const unsigned w = tid / (unsigned) kAcc, k = tid % (unsigned) kAcc;
+        double sum = 0;
+        for (unsigned r = w; r < nchunks; r += kSmWaves) sum += ((const __attribute__((address_space(1))) double *) pr.csum)[(size_t) r * kAcc + k];
+        L.red[w][k] = sum;
+    }
+    __syncthreads();
+    if (tid < (unsigned) kAcc) {
+        double sum = 0;
+        for (int w = 0; w < kSmWaves; ++w) sum += L.red[w][tid];
+        L.sum[tid] = sum;
+    }
+    __syncthreads();
+    const unsigned long long t2 = clock64();
+    ck.loop = t1 - t0, ck.red = t2 - t1;
+    return t2;
+}
 
-    // ---- 2./3. the iterations
+// ---- 3. lane 0 runs the very solve + stopping rules of the big path (icp_apply_stats, wm_icp_step.hpp) on the state in LDS
+template <class LDS>
+__device__ __forceinline__ void sm_solve(LDS &L, unsigned tid) {
+    if (tid == 0) {
+        double ex[kStatsLen];
+        expand_stats(L.st.mode, L.sum, ex);
+        icp_apply_stats(&L.st, ex);
+        L.ticket = kSmWaves;
+    }
+    __syncthreads();
+}
+
+// ---- 4. estimateLUMold on the aligned cloud (icp_pcl_functions.cpp:51-179): the sums, normal matrix and residual of
+// wm_pair_terms.hpp, which wm_info.hip runs for one pair.  The pass searches once more, under the final pose and the
+// strict gate, seeded as the iterations were.
+template <class LDS, class TG>
+__device__ __forceinline__ void sm_lumold(LDS &L, const TG &tg, const SmGrid &g, const SmallPair &pr, const SmallParams &P,
+                                          unsigned n_q, unsigned tid, SmallOut &o) {
+    float Tf[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Tf[k] = (float) L.st.T[k];
+    const float rmax_s = sqrtf(P.thr_d2_strict) * 1.0001f + 1e-6f;
+    const bool have_prev = L.st.have_prev != 0;
+    double a[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) a[k] = 0.0;
+    sm_for_queries(pr, n_q, tid, [&](unsigned q, const SmQuery &c) {
+        if (!(c.x == c.x)) return;
+        float px, py, pz;
+        xform_pcl(Tf, c.x, c.y, c.z, px, py, pz);
+        const SmMatch m = sm_seeded_search(tg, g, px, py, pz, P.thr_d2_strict, rmax_s, P.r0_cells * g.h, have_prev, c.seed);
+        pr.seed[q] = (unsigned short) (m.matched ? m.slot : 0xFFFFu);
+        if (m.matched) lum_terms(px, py, pz, tg.c(m.slot, 0), tg.c(m.slot, 1), tg.c(m.slot, 2), a);
+    });
+    sm_block_sum<16>(a, L, tid);
+    double MM[36];
+    if (tid == 0) {
+        const double *s = L.sum;
+        lum_normal_matrix(s, MM);
+        double MMinv[36];
+        inverse<6>(MM, MMinv);
+        for (int r = 0; r < 6; ++r) {
+            double d = 0;
+            for (int c = 0; c < 6; ++c) d += MMinv[r * 6 + c] * s[10 + c];
+            L.D[r] = d;
+        }
+    }
+    __syncthreads();
+    double D[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) D[k] = L.D[k];
+    double ss[1] = {0.0};
+    sm_for_queries(pr, n_q, tid, [&](unsigned, const SmQuery &c) {
+        const unsigned bslot = c.seed;
+        if (!(c.x == c.x) || bslot == 0xFFFFu) return;
+        float px, py, pz;
+        xform_pcl(Tf, c.x, c.y, c.z, px, py, pz);
+        ss[0] += lum_residual(px, py, pz, tg.c(bslot, 0), tg.c(bslot, 1), tg.c(bslot, 2), D);
+    });
+    sm_block_sum<1>(ss, L, tid);
+    if (tid == 0) {
+        const float s2 = (float) L.sum[0];
+        const bool bad = (s2 < 0.0000000000001f || !isfinite(s2));
+        // estimateLUMold falls through its failure branch (icp_pcl_functions.cpp:170-178)
+        const float inv = 1.0f / s2;
+        for (int k = 0; k < 36; ++k) o.info[k] = MM[k] * inv;
+        o.info_degenerate = bad ? 1 : 0;
+    }
+}
+
+template <class LDS>
+__device__ __forceinline__ void sm_write_out(const LDS &L, const SmGrid &g, unsigned n_tgt_fin, const SmClock &ck, bool with_info,
+                                             SmallOut &o) {
+    const IcpDevState &s = L.st;
+    for (int k = 0; k < 16; ++k) o.T[k] = s.T[k];
+    o.mse = s.mse;
+    o.prev_mse = s.prev_mse;
+    o.iterations = s.iter;
+    o.converged = s.converged;
+    o.state = s.state;
+    o.n_corr = s.n_corr;
+    o.n_target_valid = (int) n_tgt_fin;
+    o.cell = g.h;
+    o.cyc[0] = ck.loop, o.cyc[1] = ck.red, o.cyc[2] = ck.solve, o.cyc[3] = ck.setup;
+    if (!with_info) o.info_degenerate = 0;
+}
+
+// one workgroup = one registration of the queue: the steps above, in order
+template <bool INLDS>
+__global__ void __launch_bounds__(kSmThreads)
+    k_icp_small(const SmallPair *__restrict__ pairs, SmallParams P, IcpDevState st0, SmallOut *__restrict__ out) {
+    using LDS = typename std::conditional<INLDS, SmallLds, SmallLdsH>::type;
+    __shared__ LDS L;
+    const unsigned tid = threadIdx.x;
+    const SmallPair pr = pairs[blockIdx.x];
+    const unsigned long long cyc_begin = clock64();
+    constexpr unsigned kMaxT = INLDS ? (unsigned) kSmMaxTgt : (unsigned) kSmMaxTgtHbm;
+    const unsigned n_tgt = pr.n_tgt < kMaxT ? pr.n_tgt : kMaxT;  // (host checked)
+    if (tid == 0) {
+        L.st = st0;
+        L.st.prev_mse = pr.prev_mse0;
+        L.ticket = kSmWaves;
+    }
+    const unsigned n_q = sm_order_source<INLDS>(L, pr, P.stride, tid);  // 0.
+    unsigned n_tgt_fin;
+    const SmGrid g = sm_fit_grid(L, pr.tgt, n_tgt, P.stride, INLDS ? kSmCells : kSmCellsHbm, tid, n_tgt_fin);
+    const auto tg = sm_sort_target(L, pr, g, n_tgt, n_tgt_fin, P.stride, tid);  // 1.
+    const float rmax = sqrtf(P.thr_d2) * 1.0001f + 1e-6f;
+    SmClock ck = {0, 0, 0, clock64() - cyc_begin};
     for (int guard = 0; guard < P.iter_cap; ++guard) {
         if (L.st.done) break;  // (uniform: written by lane 0 before the barrier that ended the last trip)
-        float Tf[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Tf[k] = L.st.Tf[k];
-        const bool have_prev = L.st.have_prev != 0;
-        const int mode = L.st.mode;
-        double a[kAcc];
-        const unsigned long long t0 = clock64();
-        auto one_query = [&](unsigned q, const SmQuery &c) {
-            if (!(c.x == c.x)) return;  // (a non-finite point of a cloud too large to be sorted)
-            float qx, qy, qz;
-            sm_xform(Tf, c.x, c.y, c.z, qx, qy, qz);
-            unsigned long long best = sm_key(P.thr_d2, kNoIdx);
-            unsigned bslot = 0xFFFFu;
-            float r = P.r0_cells * g.h;
-            if (have_prev) {
-                // the point matched in the previous iteration is a real candidate: its distance under
-                // the NEW pose bounds the new neighbour's, so one scan of that ball certifies
-                const unsigned ps = c.seed;
-                r = rmax;
-                if (ps != 0xFFFFu) {
-                    const float d2b = sm_d2(qx, qy, qz, tg.c(ps, 0), tg.c(ps, 1), tg.c(ps, 2));
-                    if (d2b <= P.thr_d2) {
-                        best = sm_key(d2b, tg.idx(ps));
-                        bslot = ps;
-                        r = fmaxf(sqrtf(d2b) * 1.0001f + 1e-6f, 0.05f * g.h);
-                    }
-                }
-            }
-            sm_search(tg, g, qx, qy, qz, fminf(r, rmax), rmax, best, bslot);
-            const bool matched = (unsigned) best != kNoIdx;
-            pr.seed[q] = (unsigned short) (matched ? bslot : 0xFFFFu);
-            a[17] += 1.0;
-            if (!matched) return;
-            // the iteration's sums, as k_icp_stats (wm_icp.hip) forms them
-            const double px = qx, py = qy, pz = qz, tx = tg.c(bslot, 0), ty = tg.c(bslot, 1), tz = tg.c(bslot, 2);
-            a[0] += 1.0;
-            a[1] += px;
-            a[2] += py;
-            a[3] += pz;
-            if (mode == WM_ICP_SVD) {
-                a[4] += tx;
-                a[5] += ty;
-                a[6] += tz;
-                a[7] += tx * px;
-                a[8] += tx * py;
-                a[9] += tx * pz;
-                a[10] += ty * px;
-                a[11] += ty * py;
-                a[12] += ty * pz;
-                a[13] += tz * px;
-                a[14] += tz * py;
-                a[15] += tz * pz;
-            } else {
-                const double rx = px - tx, ry = py - ty, rz = pz - tz;
-                a[4] += py * py + pz * pz;
-                a[5] += -px * py;
-                a[6] += -px * pz;
-                a[7] += px * px + pz * pz;
-                a[8] += -py * pz;
-                a[9] += px * px + py * py;
-                a[10] += rx;
-                a[11] += ry;
-                a[12] += rz;
-                a[13] += py * rz - pz * ry;
-                a[14] += pz * rx - px * rz;
-                a[15] += px * ry - py * rx;
-            }
-            a[16] += (double) __uint_as_float((unsigned) (best >> 32));
-        };
-        // Chunks of 64 consecutive (cell-ordered) queries go to whichever wavefront is free: the first
-        // sixteen by wave number, the rest by a ticket in LDS -- static shares left the slowest wave
-        // 45 % behind the first.  A chunk's sums are reduced inside its wavefront (recursive halving,
-        // wm_wave.hpp) into a row of their own, so which wave took which chunk cannot change a bit of
-        // the result; the next chunk's ticket is drawn, and its loads issued, before this chunk's search.
-        {
-            unsigned c = wave;
-            bool has = c < nchunks;
-            unsigned q = c * 64u + lane;
-            SmQuery cur = {0.f, 0.f, 0.f, 0xFFFFu};
-            if (has && q < n_q) cur = sm_fetch(pr, q);
-            while (has) {
-                unsigned cn = 0;
-                if (lane == 0) cn = atomicAdd(&L.ticket, 1u);
-                cn = (unsigned) __builtin_amdgcn_readfirstlane((int) cn);
-                const bool hn = cn < nchunks;
-                const unsigned qn = cn * 64u + lane;
-                SmQuery nxt = cur;
-                if (hn && qn < n_q) nxt = sm_fetch(pr, qn);
-#pragma unroll
-                for (int k = 0; k < kAcc; ++k) a[k] = 0.0;
-                if (q < n_q) one_query(q, cur);
-                acc_halve<kAcc, 32>(a, lane);
-                const int comp = acc_comp_of_lane(lane);
-                if (comp >= 0) pr.csum[(size_t) c * kAcc + comp] = a[0];
-                c = cn, q = qn, cur = nxt, has = hn;
-            }
-        }
-        const unsigned long long t1 = clock64();
-        __threadfence_block();
-        __syncthreads();
-        if (tid < (unsigned) (kSmWaves * kAcc)) {  // the rows added in a fixed order: 16 interleaved partial sums, then those
-            const unsigned w = tid / (unsigned) kAcc, k = tid % (unsigned) kAcc;
-            double sum = 0;
-            for (unsigned c = w; c < nchunks; c += kSmWaves) sum += ((const __attribute__((address_space(1))) double *) pr.csum)[(size_t) c * kAcc + k];
-            L.red[w][k] = sum;
-        }
-        __syncthreads();
-        if (tid < (unsigned) kAcc) {
-            double sum = 0;
-            for (int w = 0; w < kSmWaves; ++w) sum += L.red[w][tid];
-            L.sum[tid] = sum;
-        }
-        __syncthreads();
-        const unsigned long long t2 = clock64();
-        if (tid == 0) {
-            double ex[kStatsLen];
-            expand_stats(mode, L.sum, ex);
-            icp_apply_stats(&L.st, ex);
-            L.ticket = kSmWaves;
-        }
-        __syncthreads();
-        cyc_loop = t1 - t0, cyc_red = t2 - t1, cyc_solve = clock64() - t2;
+        const unsigned long long t2 = sm_iteration(L, tg, g, pr, P, n_q, rmax, tid, ck);  // 2.
+        sm_solve(L, tid);                                                                 // 3.
+        ck.solve = clock64() - t2;
     }
-
-    // ---- 4. estimateLUMold on the aligned cloud (icp_pcl_functions.cpp:51-179; arithmetic of wm_info.hip)
     const bool with_info = P.with_info != 0;
-    if (with_info) {
-        float Tf[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Tf[k] = (float) L.st.T[k];
-        const float rmax_s = sqrtf(P.thr_d2_strict) * 1.0001f + 1e-6f;
-        const bool have_prev = L.st.have_prev != 0;
-        double a[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) a[k] = 0.0;
-        sm_for_queries(pr, n_q, tid, [&](unsigned q, const SmQuery &c) {
-            if (!(c.x == c.x)) return;
-            float px, py, pz;
-            sm_xform(Tf, c.x, c.y, c.z, px, py, pz);
-            unsigned long long best = sm_key(P.thr_d2_strict, kNoIdx);
-            unsigned bslot = 0xFFFFu;
-            float r = rmax_s;
-            const unsigned ps = have_prev ? c.seed : 0xFFFFu;
-            if (ps != 0xFFFFu) {
-                const float d2b = sm_d2(px, py, pz, tg.c(ps, 0), tg.c(ps, 1), tg.c(ps, 2));
-                if (d2b <= P.thr_d2_strict) {
-                    best = sm_key(d2b, tg.idx(ps));
-                    bslot = ps;
-                    r = fmaxf(sqrtf(d2b) * 1.0001f + 1e-6f, 0.05f * g.h);
-                }
-            } else if (!have_prev) {
-                r = P.r0_cells * g.h;
-            }
-            sm_search(tg, g, px, py, pz, fminf(r, rmax_s), rmax_s, best, bslot);
-            const bool matched = (unsigned) best != kNoIdx;
-            pr.seed[q] = (unsigned short) (matched ? bslot : 0xFFFFu);
-            if (!matched) return;
-            const float tx = tg.c(bslot, 0), ty = tg.c(bslot, 1), tz = tg.c(bslot, 2);
-            const float av0 = __fmul_rn(0.5f, __fadd_rn(px, tx)), av1 = __fmul_rn(0.5f, __fadd_rn(py, ty)),
-                        av2 = __fmul_rn(0.5f, __fadd_rn(pz, tz));
-            const float df0 = __fsub_rn(px, tx), df1 = __fsub_rn(py, ty), df2 = __fsub_rn(pz, tz);
-            a[0] += 1.0;
-            a[1] += av0;
-            a[2] += av1;
-            a[3] += av2;
-            a[4] += __fmul_rn(av0, av2);
-            a[5] += __fmul_rn(av0, av1);
-            a[6] += __fmul_rn(av1, av2);
-            a[7] += __fadd_rn(__fmul_rn(av1, av1), __fmul_rn(av2, av2));
-            a[8] += __fadd_rn(__fmul_rn(av0, av0), __fmul_rn(av1, av1));
-            a[9] += __fadd_rn(__fmul_rn(av0, av0), __fmul_rn(av2, av2));
-            a[10] += df0;
-            a[11] += df1;
-            a[12] += df2;
-            a[13] += __fsub_rn(__fmul_rn(av1, df2), __fmul_rn(av2, df1));
-            a[14] += __fsub_rn(__fmul_rn(av0, df1), __fmul_rn(av1, df0));
-            a[15] += __fsub_rn(__fmul_rn(av2, df0), __fmul_rn(av0, df2));
-        });
-        sm_block_sum<16>(a, L, tid);
-        double MM[36];
-        if (tid == 0) {
-            const double *s = L.sum;
-#pragma unroll
-            for (int k = 0; k < 36; ++k) MM[k] = 0.0;
-#define M_(r, c) MM[(r) * 6 + (c)]
-            M_(0, 4) = -s[2];
-            M_(0, 5) = s[3];
-            M_(1, 3) = -s[3];
-            M_(1, 4) = s[1];
-            M_(2, 3) = s[2];
-            M_(2, 5) = -s[1];
-            M_(3, 4) = -s[4];
-            M_(3, 5) = -s[5];
-            M_(4, 5) = -s[6];
-            M_(3, 3) = s[7];
-            M_(4, 4) = s[8];
-            M_(5, 5) = s[9];
-            M_(0, 0) = M_(1, 1) = M_(2, 2) = (double) (float) (int) s[0];
-            M_(4, 0) = M_(0, 4);
-            M_(5, 0) = M_(0, 5);
-            M_(3, 1) = M_(1, 3);
-            M_(4, 1) = M_(1, 4);
-            M_(3, 2) = M_(2, 3);
-            M_(5, 2) = M_(2, 5);
-            M_(4, 3) = M_(3, 4);
-            M_(5, 3) = M_(3, 5);
-            M_(5, 4) = M_(4, 5);
-#undef M_
-            double MMinv[36];
-            inverse<6>(MM, MMinv);
-            for (int r = 0; r < 6; ++r) {
-                double d = 0;
-                for (int c = 0; c < 6; ++c) d += MMinv[r * 6 + c] * s[10 + c];
-                L.D[r] = d;
-            }
-        }
-        __syncthreads();
-        double D[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) D[k] = L.D[k];
-        double ss[1] = {0.0};
-        sm_for_queries(pr, n_q, tid, [&](unsigned, const SmQuery &c) {
-            const unsigned bslot = c.seed;
-            if (!(c.x == c.x) || bslot == 0xFFFFu) return;
-            float px, py, pz;
-            sm_xform(Tf, c.x, c.y, c.z, px, py, pz);
-            const float tx = tg.c(bslot, 0), ty = tg.c(bslot, 1), tz = tg.c(bslot, 2);
-            const float av0 = __fmul_rn(0.5f, __fadd_rn(px, tx)), av1 = __fmul_rn(0.5f, __fadd_rn(py, ty)),
-                        av2 = __fmul_rn(0.5f, __fadd_rn(pz, tz));
-            const float df0 = __fsub_rn(px, tx), df1 = __fsub_rn(py, ty), df2 = __fsub_rn(pz, tz);
-            const double e0 = df0 - (D[0] + av2 * D[5] - av1 * D[4]);
-            const double e1 = df1 - (D[1] + av0 * D[4] - av2 * D[3]);
-            const double e2 = df2 - (D[2] + av1 * D[3] - av0 * D[5]);
-            ss[0] += (double) (float) (e0 * e0 + e1 * e1 + e2 * e2);
-        });
-        sm_block_sum<1>(ss, L, tid);
-        if (tid == 0) {
-            const float s2 = (float) L.sum[0];
-            const bool bad = (s2 < 0.0000000000001f || !isfinite(s2));
-            // estimateLUMold falls through its failure branch (icp_pcl_functions.cpp:170-178)
-            const float inv = 1.0f / s2;
-            SmallOut &o = out[blockIdx.x];
-            for (int k = 0; k < 36; ++k) o.info[k] = MM[k] * inv;
-            o.info_degenerate = bad ? 1 : 0;
-        }
-    }
-    if (tid == 0) {
-        SmallOut &o = out[blockIdx.x];
-        const IcpDevState &s = L.st;
-        for (int k = 0; k < 16; ++k) o.T[k] = s.T[k];
-        o.mse = s.mse;
-        o.prev_mse = s.prev_mse;
-        o.iterations = s.iter;
-        o.converged = s.converged;
-        o.state = s.state;
-        o.n_corr = s.n_corr;
-        o.n_target_valid = (int) n_tgt_fin;
-        o.cell = g.h;
-        o.cyc[0] = cyc_loop, o.cyc[1] = cyc_red, o.cyc[2] = cyc_solve, o.cyc[3] = cyc_setup;
-        if (!with_info) o.info_degenerate = 0;
-    }
+    if (with_info) sm_lumold(L, tg, g, pr, P, n_q, tid, out[blockIdx.x]);  // 4.
+    if (tid == 0) sm_write_out(L, g, n_tgt_fin, ck, with_info, out[blockIdx.x]);
 }
 
 // ------------------------------------------------------------------ host side

@@ -19,6 +19,8 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "wm_wave.hpp"
+
 namespace wm {
 
 constexpr int kRsThreads = 256;                    // threads of a scatter / histogram workgroup
@@ -53,12 +55,7 @@ __device__ __forceinline__ void rs_lds_barrier() {
 // exclusive sum over the 256 threads of a workgroup (thread t's value -> the sum of the values of threads < t)
 __device__ __forceinline__ unsigned rs_block_exclusive(unsigned v, unsigned *s_wave /*[4]*/) {
     const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off);
-        if (lane >= (unsigned) off) incl += t;
-    }
+    const unsigned incl = wave_incl_scan(v, lane);
     if (lane == 63u) s_wave[wave] = incl;
     __syncthreads();
     unsigned run = incl - v;

@@ -1,5 +1,6 @@
-// wm_wave.hpp -- wavefront-wide reduction of the ICP accumulators, shared by the correspondence kernel
-// (wm_nn.hip) and the one-workgroup registrations (wm_small.hip).
+// wm_wave.hpp -- wavefront-wide steps: the 64-lane inclusive scan and the counting sorts' scan of counts built on it, and
+// the reduction of the ICP accumulators, shared by the correspondence kernel (wm_nn.hip) and the one-workgroup
+// registrations (wm_small.hip).
 #ifndef WM_WAVE_HPP
 #define WM_WAVE_HPP
 
@@ -12,6 +13,50 @@
 #endif
 
 namespace wm {
+
+// inclusive sum of v over the lanes 0 ... lane of a wave
+__device__ __forceinline__ unsigned wave_incl_scan(unsigned v, unsigned lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned up = __shfl_up(v, off);
+        if (lane >= (unsigned) off) v += up;
+    }
+    return v;
+}
+
+// Exclusive scan of a counting sort's counts by a workgroup of THREADS lanes, four cells per thread at a time:
+// run[c] = start[c] = first slot of cell c (the counts were made by atomics, which live in L2: read there).
+// `scratch`: THREADS / 64 words of LDS.  Every thread calls.
+template <int THREADS>
+__device__ __forceinline__ void block_scan_counts(unsigned *run, unsigned *start, unsigned n_cells, unsigned *scratch) {
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    unsigned carry = 0;
+    for (unsigned c0 = 0; c0 < n_cells; c0 += 4u * THREADS) {
+        const unsigned c = c0 + 4u * tid;
+        unsigned v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = c + (unsigned) u < n_cells ? __hip_atomic_load(&run[c + (unsigned) u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const unsigned mine = v[0] + v[1] + v[2] + v[3];
+        const unsigned incl = wave_incl_scan(mine, lane);
+        if (lane == 63) scratch[wave] = incl;
+        __syncthreads();
+        unsigned base = carry, all = 0;
+        for (unsigned w = 0; w < (unsigned) (THREADS / 64); ++w) {
+            if (w < wave) base += scratch[w];
+            all += scratch[w];
+        }
+        unsigned at = base + incl - mine;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (c + (unsigned) u < n_cells) {
+                run[c + (unsigned) u] = at;
+                start[c + (unsigned) u] = at;
+                at += v[u];
+            }
+        carry += all;
+        __syncthreads();
+    }
+}
 
 // Wave reduction of kAcc doubles by recursive halving: at the step for lane bit M a lane keeps one
 // half of its values and sends the other half to lane ^ M, so the 18 values cost 9+5+3+2+1+1 = 21
