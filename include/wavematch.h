@@ -1046,6 +1046,67 @@ int wm_sac_segment_batch(wm_ctx *ctx, const wm_sac_scan *scans, int n_scans, siz
                          int *status /* host, n_scans entries */, wm_sac_stats *stats /* NULL ok: n_scans entries */,
                          float *kernel_ms /* NULL ok */);
 
+/* ------------------------------------------------------------- cluster boxes */
+/* Where each cluster is and how big it is, on the device: what pcl::MomentOfInertiaEstimation (getMassCenter, getAABB,
+ * getOBB, getEigenValues, getEigenVectors), pcl::getMinMax3D and pcl::compute3DCentroid give for one cluster at a
+ * time, here for every cluster of a member list in one call.  [PCL-upstream: restated from PCL 1.8
+ * features/impl/moment_of_inertia_estimation.hpp (computeOBB, the mean and the covariance's eigenvectors) and
+ * common/impl/common.hpp (getMinMax3D); no PCL on the build machine]  (tests/boxes_reference.py is the checker).  All
+ * arithmetic is as written here, every operation rounded and nothing fused.
+ *   members      member e of the list is record indices[e] of pts (indices == NULL: record e); cluster c is members
+ *                [offsets[c], offsets[c + 1]).  A member with a non-finite coordinate is skipped and sets
+ *                WM_BOX_NONFINITE; n counts the finite members; n == 0 sets WM_BOX_EMPTY and every other field is zero.
+ *   aabb         componentwise min and max of the members' floats, ordered by their orderable-integer keys (the sign
+ *                bit flipped for a positive float, every bit for a negative one), so -0 < +0.  Exact.
+ *   sums         a = aabb_min widened to double; per member d = (double) p - a (every component >= 0); the nine terms
+ *                d.x, d.y, d.z, d.x d.x, d.x d.y, d.x d.z, d.y d.y, d.y d.z, d.z d.z are formed in double and each
+ *                term t enters as the integer trunc(t * 2^56).  The integers are added exactly: a sum is a function of
+ *                the member SET, not of order, wave or workgroup.  A component of aabb_max - a (in double) of 2^20 m or
+ *                more sets WM_BOX_RANGE: the moment, axes and OBB fields are zero, n and the AABB stay valid.
+ *   centroid,    S1 and S2 are the totals * 2^-56 as doubles (the integer total rounded once); m = S1 / n; centroid =
+ *   covariance   (float) (a + m); C = S2 / n - m m^T (the quotient, the product and the difference each rounded).
+ *                DEVIATION: PCL sums the uncentred floats in float and subtracts a float mean.
+ *   axes         the symmetric eigen-decomposition of C in double (cyclic Jacobi).  Eigenvalues are clamped at 0 and
+ *                sorted descending (equal ones keep the order x, y, z of the Jacobi diagonal); major and middle are each
+ *                flipped so that their component of largest magnitude is positive (the lowest index on ties); minor =
+ *                major x middle.  If the largest eigenvalue is 0 the axes are the identity.  Values and axes are
+ *                rounded to float on output.  DEVIATION: PCL leaves the signs to Eigen::EigenSolver.
+ *   OBB          PCL's computeOBB on the RETURNED floats of centroid and axes, widened to double: per member e =
+ *                (double) p - centroid, s_k = (e.x a_k.x + e.y a_k.y) + e.z a_k.z; lo_k / hi_k the min / max of s_k over
+ *                the members; obb_half[k] = (float) ((hi_k - lo_k) / 2); obb_center[i] = (float) (((centroid[i] +
+ *                mid_0 a_0[i]) + mid_1 a_1[i]) + mid_2 a_2[i]), mid_k = (hi_k + lo_k) / 2.  Min and max know no order:
+ *                given the returned centroid and axes these six floats are exact.
+ *   determinism  two calls give identical bytes; permuting the members inside the clusters gives identical bytes. */
+typedef struct {                 /* 128 bytes, one per cluster */
+    uint32_t n;                  /* finite members */
+    uint32_t flags;              /* WM_BOX_* */
+    float aabb_min[3], aabb_max[3];
+    float centroid[3];
+    float eigenvalues[3];        /* of the covariance, descending: major, middle, minor; >= 0 */
+    float axes[9];               /* rows: major, middle, minor; orthonormal, right-handed */
+    float obb_center[3];         /* PCL getOBB's position */
+    float obb_half[3];           /* half extents along the axes (PCL's max_point_OBB) */
+    uint32_t reserved[3];        /* zero */
+} wm_cluster_box;
+enum { WM_BOX_EMPTY = 1, WM_BOX_NONFINITE = 2, WM_BOX_RANGE = 4 };
+
+/* The boxes of n_clusters clusters over n records of `stride_bytes` (x y z first) in `mem`.  offsets has n_clusters + 1
+ * entries; `list_mem` says where indices and offsets live, `out_mem` where boxes_out (n_clusters entries) lives.  The
+ * call takes wm_cluster_extract's indices_out / offsets_out together with its input cloud, and
+ * wm_cluster_extract_batch's points_out / offsets_out with indices == NULL (then n_members must equal n): one call
+ * covers the clusters of all scans.  The number of launches and host waits does not depend on n_clusters or n_members.
+ * Argument errors, found before a device is touched: a null ctx; with n_clusters > 0 a null offsets / boxes_out; a bad
+ * stride, mem, list_mem or out_mem; n, n_members or n_clusters above 0x7FFFFFF0; a null pts with n > 0; indices == NULL with
+ * n_members != n.  n_clusters == 0: WM_OK with no device touched.  Found on the device, counted there and brought back
+ * in the call's one final fetch: offsets that do not ascend, offsets[0] != 0, offsets[n_clusters] != n_members, an
+ * index outside [0, n) -- each gives WM_ERR_ARG with boxes_out unspecified; no kernel reads out of range because of
+ * them.  kernel_ms (NULL ok): device time from the upload to the last box.  The workspace is the context's own (freed
+ * by wm_ctx_destroy); the registration state and the ground, outlier, cluster and SAC workspaces are not touched. */
+int wm_cluster_boxes(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                     const int32_t *indices /* NULL ok */, size_t n_members,
+                     const uint32_t *offsets, size_t n_clusters, int list_mem,
+                     wm_cluster_box *boxes_out, int out_mem, float *kernel_ms /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -164,6 +164,20 @@ WM_SAC_PLANE, WM_SAC_PERPENDICULAR_PLANE, WM_SAC_PARALLEL_PLANE = 0, 1, 2
 WM_SAC_NONE, WM_SAC_INLIER, WM_SAC_OUTLIER = 0, 1, 2
 
 
+class ClusterBox(C.Structure):
+    """wm_cluster_box: 128 bytes per cluster (BOX_DTYPE is the same layout for numpy)."""
+    _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3),
+                ("centroid", C.c_float * 3), ("eigenvalues", C.c_float * 3), ("axes", C.c_float * 9),
+                ("obb_center", C.c_float * 3), ("obb_half", C.c_float * 3), ("reserved", C.c_uint32 * 3)]
+
+
+BOX_DTYPE = np.dtype([("n", np.uint32), ("flags", np.uint32), ("aabb_min", np.float32, 3), ("aabb_max", np.float32, 3),
+                      ("centroid", np.float32, 3), ("eigenvalues", np.float32, 3), ("axes", np.float32, (3, 3)),
+                      ("obb_center", np.float32, 3), ("obb_half", np.float32, 3), ("reserved", np.uint32, 3)])
+WM_BOX_EMPTY, WM_BOX_NONFINITE, WM_BOX_RANGE = 1, 2, 4
+assert C.sizeof(ClusterBox) == 128 and BOX_DTYPE.itemsize == 128
+
+
 class SacParams(C.Structure):
     _fields_ = [("model", C.c_int), ("distance_threshold", C.c_double), ("max_iterations", C.c_int),
                 ("probability", C.c_double), ("optimize_coefficients", C.c_int), ("axis", C.c_double * 3),
@@ -345,6 +359,8 @@ def lib():
                                                C.POINTER(ClusterParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
                                                C.POINTER(C.c_size_t), C.POINTER(ClusterStats), C.POINTER(C.c_float)]
+        L.wm_cluster_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]
         L.wm_sac_default_params.argtypes = [C.POINTER(SacParams)]
         L.wm_sac_default_params.restype = None
         L.wm_sac_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(SacParams),
@@ -992,6 +1008,53 @@ class Context:
         if not points:
             return out
         return out, kept[:m.value], np.array(pt_offs, np.int64)
+
+    def cluster_boxes(self, cloud, offsets, indices=None, out_mem=None, timing=None):
+        """Count, AABB, centroid, eigenvalues, axes and oriented box of every cluster of a member list
+        (wm_cluster_boxes) -> a structured array of BOX_DTYPE, one row per cluster, for host output; a torch uint8
+        tensor (n_clusters, 128) for device output (its .cpu().numpy().view(BOX_DTYPE)[:, 0] are the same rows).
+        `cloud`: float32 (n, 3|4) numpy array or HIP torch tensor.  `offsets` (n_clusters + 1) and `indices` (int32, or
+        None: member e is record e) are cluster_extract's outputs, both numpy arrays or both HIP torch tensors (int32
+        tensors carry the uint32 bits).  out_mem: by default where the cloud lives.  timing: a dict that receives
+        kernel_ms."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+
+        def list_arg(a, dtype):
+            if a is None:
+                return None, None, None
+            if isinstance(a, np.ndarray):
+                a = np.ascontiguousarray(a).astype(dtype, copy=False)
+                return a.ctypes.data, WM_MEM_HOST, a
+            import torch
+            assert isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.dim() == 1
+            a = a.contiguous()
+            return a.data_ptr(), WM_MEM_DEVICE if a.is_cuda else WM_MEM_HOST, a
+
+        off_ptr, list_mem, off = list_arg(offsets, np.uint32)
+        idx_ptr, idx_mem, idx = list_arg(indices, np.int32)
+        assert idx_mem in (None, list_mem), "offsets and indices live in one memory"
+        n_clusters = max(len(off) - 1, 0)
+        n_members = len(idx) if idx is not None else n
+        out_mem = mem if out_mem is None else out_mem
+        ms = C.c_float(0)
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            out = torch.zeros((n_clusters, 128), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+            out_ptr = out.data_ptr()
+        else:
+            if mem == WM_MEM_DEVICE or list_mem == WM_MEM_DEVICE:
+                import torch
+                torch.cuda.synchronize()
+            out = np.zeros(n_clusters, BOX_DTYPE)
+            out_ptr = out.ctypes.data
+        self._check(lib().wm_cluster_boxes(self._h, C.c_void_p(ptr), n, stride, mem, C.c_void_p(idx_ptr), n_members,
+                                           C.c_void_p(off_ptr), n_clusters, list_mem, C.c_void_p(out_ptr), out_mem,
+                                           C.byref(ms)), "wm_cluster_boxes")
+        if timing is not None:
+            timing["kernel_ms"] = ms.value
+        return out
 
     def ground_segment_batch(self, clouds, params=None, keep=WM_KEEP_OBSTACLE | WM_KEEP_OVERHANGING, points=False):
         """The filter for a queue of scans in one device call (wm_ground_segment_batch) -> [(labels, indices,

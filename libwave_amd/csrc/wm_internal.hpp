@@ -347,6 +347,7 @@ struct wm_ctx {
     void *outlier = nullptr;                // wm_outlier.hip: the outlier filters' workspace (its own as well)
     void *cluster = nullptr;                // wm_cluster.hip: the cluster extraction's workspace (its own as well)
     void *sac = nullptr;                    // wm_sac.hip: the plane segmentation's workspace (its own as well)
+    void *boxes = nullptr;                  // wm_describe.hip: the cluster boxes' workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -662,6 +663,9 @@ void cluster_release(wm_ctx *ctx);
 
 // ---- wm_sac.hip
 void sac_release(wm_ctx *ctx);
+
+// ---- wm_describe.hip
+void boxes_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0

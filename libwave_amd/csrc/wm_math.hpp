@@ -423,4 +423,52 @@ WM_HD bool gn6_from_stats(const double *st, double *T) {
     return ok;
 }
 
+// One Jacobi rotation of a symmetric 3 x 3 matrix A (full storage) that annihilates A[P][Q]; V's columns follow.
+// (compile-time indices: the nine entries stay in registers)
+template <int P, int Q>
+WM_HD void jacobi3_rotate(double *A, double *V) {
+    constexpr int R = 3 - P - Q;  // the third index
+    const double apq = A[P * 3 + Q];
+    if (apq == 0.0) return;
+    const double app = A[P * 3 + P], aqq = A[Q * 3 + Q];
+    // an off-diagonal entry below 2^-60 of its diagonal pair changes neither value nor residual at double precision
+    if (fabs(apq) <= 8.673617379884035e-19 * (fabs(app) + fabs(aqq))) {
+        A[P * 3 + Q] = A[Q * 3 + P] = 0.0;
+        return;
+    }
+    const double theta = (aqq - app) / (2.0 * apq);
+    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));  // (theta = inf: t = 0)
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+    A[P * 3 + P] = app - t * apq;
+    A[Q * 3 + Q] = aqq + t * apq;
+    A[P * 3 + Q] = A[Q * 3 + P] = 0.0;
+    const double arp = A[R * 3 + P], arq = A[R * 3 + Q];
+    A[R * 3 + P] = A[P * 3 + R] = c * arp - s * arq;
+    A[R * 3 + Q] = A[Q * 3 + R] = s * arp + c * arq;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double vrp = V[r * 3 + P], vrq = V[r * 3 + Q];
+        V[r * 3 + P] = c * vrp - s * vrq;
+        V[r * 3 + Q] = s * vrp + c * vrq;
+    }
+}
+
+// Eigen-decomposition of a symmetric 3 x 3 matrix by cyclic Jacobi sweeps: w[k] and column k of V (unsorted).  A is
+// destroyed.  Ends when the off-diagonal is exactly zero, which the cut-off above brings about; 32 sweeps bound it.
+// (Host and device, for the cluster boxes.  The NDT voxel model keeps its own device-only sym_eig3, wm_ndt_dev.hpp, whose
+// stopping rule and ascending order its golden results are pinned to.)
+WM_HD void jacobi3(double *A, double *w, double *V) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        if (A[1] == 0.0 && A[2] == 0.0 && A[5] == 0.0) break;
+        jacobi3_rotate<0, 1>(A, V);
+        jacobi3_rotate<0, 2>(A, V);
+        jacobi3_rotate<1, 2>(A, V);
+    }
+    w[0] = A[0];
+    w[1] = A[4];
+    w[2] = A[8];
+}
+
 }  // namespace wm
