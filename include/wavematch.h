@@ -885,6 +885,57 @@ int wm_cluster_extract(wm_ctx *ctx, const void *pts, size_t n, size_t stride_byt
                        uint32_t *offsets_out, size_t cap_clusters,    /* cap_clusters + 1 entries */
                        int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats /* NULL ok */);
 
+/* pcl::ConditionalEuclideanClustering with a normal and / or a scalar test on every edge: what keeps a parked car
+ * apart from the wall it stands against, or a kerb from the road.  [PCL-upstream: restated from PCL 1.8
+ * segmentation/impl/conditional_euclidean_clustering.hpp; no PCL on the build machine]
+ * (tests/cluster_cond_reference.py is the checker):
+ *   attributes   `attr` holds n records of attr_stride bytes (>= 16, a multiple of 4) in attr_mem, record i belonging to
+ *                point i; each begins with four floats (a0, a1, a2, s).  That is what wm_estimate_normals writes
+ *                (nx, ny, nz, curvature), so its device output goes in as it is; s is whatever the caller puts there,
+ *                an intensity for one.
+ *   edges        two different finite points i, j are joined iff ALL of
+ *                  d2 < r2, exactly as in wm_cluster_extract;
+ *                  with WM_CLUSTER_COND_NORMAL: fabsf(dot) >= cos_min, dot = (a0_i * a0_j + a1_i * a1_j) + a2_i * a2_j
+ *                    in float with every operation rounded and nothing fused, cos_min = (float) cos(max_normal_angle)
+ *                    with the cosine taken in double;
+ *                  with WM_CLUSTER_COND_SCALAR: fabsf(s_i - s_j) <= (float) max_scalar_diff, the subtraction one float
+ *                    operation.
+ *                Both tests are symmetric in i and j bit for bit, so the relation is an undirected graph and PCL's
+ *                region growing returns its connected components whatever the seed order.  A NaN anywhere makes its
+ *                comparison false: a finite point with NaN attributes is a component of its own, and so is one with
+ *                the (0, 0, 0, .) normal wm_estimate_normals gives a degenerate neighbourhood as long as cos_min > 0
+ *                -- a cluster of one point, not WM_CLUSTER_NONE.  (float) cos(pi / 2) is 6.1e-17, not 0: exactly
+ *                perpendicular normals are separate even at max_normal_angle = pi / 2.  Switching the test off is what
+ *                `flags` is for.
+ *   the rest     the size rule, the order of the clusters and of their members, the labels, the capacities and their
+ *                WM_ERR_ARG rule, n == 0, a cloud without a finite point (its attributes do not matter: a non-finite
+ *                point is WM_CLUSTER_NONE), the workspace and the determinism are wm_cluster_extract's, word for word.
+ *   flags == 0   attr may be NULL; the call returns byte for byte what wm_cluster_extract returns, from the same
+ *                kernels.
+ *   deviations   from PCL's class: the condition is one of these fixed tests, not a caller's function (and so always
+ *                symmetric); PCL returns the clusters in seed order, here they are ordered as wm_cluster_extract's;
+ *                there is no getRemovedClusters (labels_out says WM_CLUSTER_REJECTED instead).
+ * Argument errors, found before a device is touched: wm_cluster_extract's; a null c; flags outside 0 ... 3;
+ * reserved != 0; flags != 0 with a null attr and n > 0; an attr_stride below 16 or no multiple of 4, or a bad attr_mem
+ * (both whatever the flags); with WM_CLUSTER_COND_NORMAL an angle that is not finite or outside [0, pi / 2]; with
+ * WM_CLUSTER_COND_SCALAR a difference that is not finite or negative. */
+enum { WM_CLUSTER_COND_NORMAL = 1, WM_CLUSTER_COND_SCALAR = 2 };
+typedef struct {
+    int flags;                /* OR of WM_CLUSTER_COND_*; 0: no edge test */
+    int reserved;             /* 0 */
+    double max_normal_angle;  /* radians, 0 ... pi/2; read with WM_CLUSTER_COND_NORMAL */
+    double max_scalar_diff;   /* finite, >= 0;    read with WM_CLUSTER_COND_SCALAR */
+} wm_cluster_cond;            /* 24 bytes */
+void wm_cluster_cond_default(wm_cluster_cond *c);   /* all zero */
+
+int wm_cluster_extract_cond(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                            const void *attr, size_t attr_stride, int attr_mem,
+                            const wm_cluster_params *p, const wm_cluster_cond *c,
+                            /* from here on exactly wm_cluster_extract's outputs */
+                            int32_t *labels_out, int32_t *indices_out, size_t cap,
+                            uint32_t *offsets_out, size_t cap_clusters, int out_mem,
+                            size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats);
+
 /* A queue of scans in one device call: the same kernels with a scan dimension, one `p`, one stride and one `mem` for
  * the batch (as wm_ground_segment_batch).  The clusters of the batch are numbered scan after scan: scan k's are
  * [cluster_first[k], cluster_first[k + 1]), cluster_first[n_scans] is their number in all, and cluster g is

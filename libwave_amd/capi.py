@@ -155,6 +155,16 @@ class ClusterScan(C.Structure):
     _fields_ = [("pts", C.c_void_p), ("n", C.c_size_t)]
 
 
+class ClusterCond(C.Structure):
+    """wm_cluster_cond: the edge tests of wm_cluster_extract_cond (24 bytes)."""
+    _fields_ = [("flags", C.c_int), ("reserved", C.c_int), ("max_normal_angle", C.c_double),
+                ("max_scalar_diff", C.c_double)]
+
+
+WM_CLUSTER_COND_NORMAL, WM_CLUSTER_COND_SCALAR = 1, 2
+assert C.sizeof(ClusterCond) == 24
+
+
 WM_CLUSTER_NONE, WM_CLUSTER_REJECTED = -1, -2
 WM_CLUSTER_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of a cluster_extract_batch's scans in all
 WM_CLUSTER_BATCH_MAX_SCANS = 0x1000000
@@ -355,6 +365,12 @@ def lib():
         L.wm_cluster_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(ClusterParams),
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
+        L.wm_cluster_cond_default.argtypes = [C.POINTER(ClusterCond)]
+        L.wm_cluster_cond_default.restype = None
+        L.wm_cluster_extract_cond.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                              C.c_int, C.POINTER(ClusterParams), C.POINTER(ClusterCond), C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                              C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]
         L.wm_cluster_extract_batch.argtypes = [C.c_void_p, C.POINTER(ClusterScan), C.c_int, C.c_size_t, C.c_int,
                                                C.POINTER(ClusterParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                                C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t),
@@ -449,6 +465,45 @@ def cluster_params(params=None, **kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def cluster_cond(cond=None, max_normal_angle=None, max_scalar_diff=None, **kw):
+    """wm_cluster_cond from wm_cluster_cond_default (no test), a ClusterCond or a dict of field values, and keywords.
+    max_normal_angle= (radians) and max_scalar_diff= each ENABLE their test unless `flags` is given as well."""
+    c = ClusterCond()
+    lib().wm_cluster_cond_default(C.byref(c))
+    if isinstance(cond, ClusterCond):
+        cond = {k: getattr(cond, k) for k, _ in ClusterCond._fields_}
+    for k, v in dict(cond or {}).items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    if max_normal_angle is not None:
+        c.max_normal_angle = max_normal_angle
+        c.flags |= WM_CLUSTER_COND_NORMAL
+    if max_scalar_diff is not None:
+        c.max_scalar_diff = max_scalar_diff
+        c.flags |= WM_CLUSTER_COND_SCALAR
+    for k, v in kw.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+def _attr_arg(a, n):
+    """-> (pointer, stride, mem, keepalive) of an attribute array: float32 (n, 4) numpy array or HIP torch tensor; None:
+    no attributes (a call without an edge test)."""
+    if a is None:
+        return None, 16, WM_MEM_HOST, None
+    if isinstance(a, np.ndarray):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert a.ndim == 2 and a.shape == (n, 4)
+        return a.ctypes.data, 16, WM_MEM_HOST, a
+    import torch
+    assert isinstance(a, torch.Tensor) and a.dtype == torch.float32 and tuple(a.shape) == (n, 4)
+    a = a.contiguous()
+    return a.data_ptr(), 16, WM_MEM_DEVICE if a.is_cuda else WM_MEM_HOST, a
 
 
 def sac_params(params=None, **kw):
@@ -790,6 +845,19 @@ class Context:
         tensor.  out_mem: where the three arrays are written, WM_MEM_HOST (numpy arrays) or WM_MEM_DEVICE (torch
         tensors); by default where the cloud lives.  `params`: a ClusterParams, a dict of its fields, or None (PCL's
         defaults: the tolerance must then come as a keyword); keywords override fields."""
+        return self._cluster_extract(cloud, None, None, params, labels, out_mem, kw)
+
+    def cluster_extract_cond(self, cloud, attr, cond=None, params=None, labels=True, out_mem=None, **kw):
+        """pcl::ConditionalEuclideanClustering with a normal and / or scalar test on every edge
+        (wm_cluster_extract_cond) -> cluster_extract's dict.  `attr`: float32 (n, 4) numpy array or HIP torch tensor,
+        (a0, a1, a2, s) per point -- estimate_normals' output as it is; None only without a test.  `cond`: a
+        ClusterCond, a dict of its fields, or None (no test: cluster_extract's bytes); the keywords max_normal_angle=
+        and max_scalar_diff= enable their test (see cluster_cond), every other keyword is cluster_extract's."""
+        ck = {k: kw.pop(k) for k in ("max_normal_angle", "max_scalar_diff") if k in kw}
+        return self._cluster_extract(cloud, attr, cluster_cond(cond, **ck), params, labels, out_mem, kw)
+
+    def _cluster_extract(self, cloud, attr, cond, params, labels, out_mem, kw):
+        """The body of cluster_extract and cluster_extract_cond (cond None: wm_cluster_extract)."""
         ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
         if isinstance(params, ClusterParams):
             params = {k: getattr(params, k) for k, _ in ClusterParams._fields_}
@@ -814,9 +882,16 @@ class Context:
 
             def addr(a):
                 return C.c_void_p(a.ctypes.data) if a is not None else None
-        rc = self._check(lib().wm_cluster_extract(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), addr(lab), addr(idx),
-                                                  n, addr(off), n, out_mem, C.byref(k), C.byref(m), C.byref(st)),
-                         "wm_cluster_extract")
+        if cond is None:
+            rc = self._check(lib().wm_cluster_extract(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), addr(lab),
+                                                      addr(idx), n, addr(off), n, out_mem, C.byref(k), C.byref(m),
+                                                      C.byref(st)), "wm_cluster_extract")
+        else:
+            aptr, astride, amem, keep_attr = _attr_arg(attr, n)
+            rc = self._check(lib().wm_cluster_extract_cond(self._h, C.c_void_p(ptr), n, stride, mem, C.c_void_p(aptr),
+                                                           astride, amem, C.byref(p), C.byref(cond), addr(lab), addr(idx),
+                                                           n, addr(off), n, out_mem, C.byref(k), C.byref(m), C.byref(st)),
+                             "wm_cluster_extract_cond")
         out = dict(rc=rc, labels=lab[:n] if labels else None, indices=idx[:m.value], offsets=off[:k.value + 1],
                    n_clusters=k.value, n_out=m.value)
         out.update({f: getattr(st, f) for f, _ in ClusterStats._fields_})

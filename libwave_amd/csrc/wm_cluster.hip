@@ -23,6 +23,13 @@
 // grid's atomics (see k_outlier_moments' note) -- so a root's number never reaches an output: the order of the
 // clusters comes from (size, smallest caller index) alone.
 //
+// wm_cluster_extract_cond (pcl::ConditionalEuclideanClustering with a normal and / or scalar test on every edge; the
+// checker is tests/cluster_cond_reference.py) is the single call with two launches in place of the link's one:
+// k_cluster_attr brings the caller's four floats per point into the grid's order, and k_cluster_link<true> asks them
+// about every pair that passes the distance test before it joins the pair.  Both tests are symmetric in their two
+// points, so the clusters are still the connected components of an undirected graph and nothing behind the link
+// changes.  flags == 0 launches k_cluster_link<false>, which is the kernel wm_cluster_extract launches.
+//
 // A batch (ClScan: a scan's row of the device table; tab == nullptr is the single call, its scan handed over by
 // value): its front -- the table, the packed batch positions, a lattice per scan inside ONE cell-sorted array of grid
 // positions -- is wm_scan_batch.hpp's, shared with wm_outlier_filter_batch.  A scan's GridDev points at its own slice
@@ -98,8 +105,29 @@ __global__ void __launch_bounds__(kBlock) k_cluster_init(unsigned *__restrict__ 
 // A batch: a workgroup (one wave) belongs to one scan, found from the table of first workgroups, so the scan's
 // lattice is the same for every lane (scalar registers) and its runs hold the scan's own points only; the positions
 // it joins are the batch's.
+//
+// COND (wm_cluster_extract_cond with flags != 0): an edge that passes the distance test must also pass the enabled
+// tests on the two points' attributes, attr_g (grid order, written by k_cluster_attr in an earlier launch on the
+// stream: plain loads).  The lane's own record is loaded once; the candidate's only behind j < i and d2 < r2, so a
+// candidate that fails the distance test costs no attribute traffic.  Both tests are symmetric in their two points bit
+// for bit (products and sums commute, fabsf(a - b) == fabsf(b - a)), and a NaN on either side fails the comparison.
+struct LinkCond {
+    const float4 *attr_g;
+    int flags;               // WM_CLUSTER_COND_*
+    float cos_min, max_diff;  // (float) cos(max_normal_angle), (float) max_scalar_diff
+};
+
+__device__ __forceinline__ bool cond_holds(const LinkCond &c, const float4 &a, const float4 &b) {
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z));
+    const bool normal = !(c.flags & WM_CLUSTER_COND_NORMAL) || fabsf(dot) >= c.cos_min;
+    const bool scalar = !(c.flags & WM_CLUSTER_COND_SCALAR) || fabsf(__fsub_rn(a.w, b.w)) <= c.max_diff;
+    return normal && scalar;
+}
+
+template <bool COND>
 __global__ void __launch_bounds__(kLinkBlock)
-    k_cluster_link(GridDev g, const ClScan *__restrict__ tab, unsigned S, unsigned n, float r2, float rf, unsigned *parent) {
+    k_cluster_link(GridDev g, const ClScan *__restrict__ tab, unsigned S, unsigned n, float r2, float rf, unsigned *parent,
+                   LinkCond cond) {
     __shared__ uint2 s_runs[kKnnRows * kLinkBlock];
     unsigned i = blockIdx.x * kLinkBlock + threadIdx.x;
     if (tab) {
@@ -110,10 +138,25 @@ __global__ void __launch_bounds__(kLinkBlock)
     }
     if (i >= n) return;
     const float4 q = g.pts[i];
+    float4 own = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (COND) own = cond.attr_g[i];
     radius_walk<false>(g, q, rf * g.inv_h, s_runs, threadIdx.x, kLinkBlock, [&](unsigned j, const float4 &t) {
-        if (j < i && g_d2(q.x, q.y, q.z, t) < r2) uf_union(parent, i, j);
+        if (j < i && g_d2(q.x, q.y, q.z, t) < r2) {
+            if (!COND || cond_holds(cond, own, cond.attr_g[j])) uf_union(parent, i, j);
+        }
         return false;
     });
+}
+
+// One lane per grid position: the caller's four floats (record pts[i].w of `raw`, attr_stride bytes each) into the
+// grid's order, so that the link kernel's attribute reads have the locality its point reads have.
+__global__ void __launch_bounds__(kBlock)
+    k_cluster_attr(const float4 *__restrict__ gpts, unsigned n, const unsigned char *__restrict__ raw, size_t attr_stride,
+                   float4 *__restrict__ attr_g) {
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float *a = reinterpret_cast<const float *>(raw + (size_t) __float_as_uint(gpts[i].w) * attr_stride);
+    attr_g[i] = make_float4(a[0], a[1], a[2], a[3]);
 }
 
 // (behind the link launch: the forest is final, a find only shortens paths)  c: the point's batch position
@@ -254,6 +297,7 @@ struct ClusterWs {
     DevBuf parent, root_of, min_idx, size, keep, pos, rank_of, lrank_of, size_by_rank, off, labels, offsets, res;
     DevBuf keys_a, keys_b, vals_a, vals_b, sort_tmp;  // the two sorts' ping-pong pairs
     DevBuf idx, pout;                                 // host outputs on their way
+    DevBuf attr_raw, attr_g;  // wm_cluster_extract_cond: host attributes uploaded, and the four floats in grid order
     ScanBatchBufs sb;  // the packed cloud and its grid; a batch's front (wm_scan_batch.hpp)
     PinnedBuf h_res;   // the counters, four per scan
 };
@@ -263,7 +307,7 @@ void cluster_release(wm_ctx *ctx) {
     if (!w) return;
     DevBuf *bufs[] = {&w->parent, &w->root_of, &w->min_idx, &w->size, &w->keep, &w->pos, &w->rank_of,
                       &w->lrank_of, &w->size_by_rank, &w->off, &w->labels, &w->offsets, &w->res, &w->keys_a, &w->keys_b,
-                      &w->vals_a, &w->vals_b, &w->sort_tmp, &w->idx, &w->pout};
+                      &w->vals_a, &w->vals_b, &w->sort_tmp, &w->idx, &w->pout, &w->attr_raw, &w->attr_g};
     for (DevBuf *b : bufs) b->release();
     w->sb.release();
     w->h_res.release();
@@ -313,6 +357,9 @@ struct ClCall {
     size_t out_stride = 0;
     uint32_t *offsets_out = nullptr;
     size_t cap_clusters = 0;
+    LinkCond cond{};                          // flags != 0: wm_cluster_extract_cond's edge tests (attr_g set by cl_back)
+    const unsigned char *attr_raw = nullptr;  // the caller's attribute records in device memory
+    size_t attr_stride = 0;
     size_t m = 0, kept = 0;  // results: the kept clusters and their points; the counters are in w.h_res
     float ms = 0.f;
 };
@@ -382,7 +429,17 @@ int cl_back(wm_ctx *ctx, ClusterWs &w, ClCall &c) {
     WM_HIP(ctx, hipMemsetAsync(size, 0, n_finite * 4, st));
     WM_HIP(ctx, hipMemsetAsync(res, 0, (size_t) S * 4 * sizeof(unsigned), st));
     hipLaunchKernelGGL(k_cluster_init, dim3(fblocks), dim3(kBlock), 0, st, parent, nf);
-    hipLaunchKernelGGL(k_cluster_link, dim3(c.link_blocks), dim3(kLinkBlock), 0, st, g, tab, S, nf, r2, rf, parent);
+    if (c.cond.flags) {  // two launches in place of one: the attributes into grid order, the link with its edge tests
+        WM_HIP(ctx, w.attr_g.reserve(n_finite * sizeof(float4)));
+        c.cond.attr_g = w.attr_g.as<float4>();
+        hipLaunchKernelGGL(k_cluster_attr, dim3(fblocks), dim3(kBlock), 0, st, g.pts, nf, c.attr_raw, c.attr_stride,
+                           w.attr_g.as<float4>());
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cluster_link<true>), dim3(c.link_blocks), dim3(kLinkBlock), 0, st, g, tab, S, nf, r2,
+                           rf, parent, c.cond);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cluster_link<false>), dim3(c.link_blocks), dim3(kLinkBlock), 0, st, g, tab, S, nf, r2,
+                           rf, parent, LinkCond{});
+    }
     hipLaunchKernelGGL(k_cluster_flatten, dim3(fblocks), dim3(kBlock), 0, st, g.pts, nf, parent, root_of, min_idx, size);
     const unsigned lo = (unsigned) std::max(c.p->min_cluster_size, 1), hi = (unsigned) c.p->max_cluster_size;
     hipLaunchKernelGGL(k_cluster_roots, dim3(fblocks), dim3(kBlock), 0, st, (const unsigned *) size, nf, lo, hi, keep, res,
@@ -484,7 +541,8 @@ void cl_stats_out(const unsigned *h, size_t n_finite, float ms, wm_cluster_stats
 // wm_cluster_extract_batch for a batch of one (arguments checked by the callers; the outputs zeroed).
 int cl_one(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const wm_cluster_params *p, int32_t *labels_out,
            int32_t *indices_out, size_t cap, void *points_out, size_t out_stride, uint32_t *offsets_out, size_t cap_clusters,
-           int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats, float *kernel_ms) {
+           int out_mem, size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats, float *kernel_ms,
+           const LinkCond *cond = nullptr, const void *attr = nullptr, size_t attr_stride = 0, int attr_mem = WM_MEM_HOST) {
     ClCall c;
     c.host_out = out_mem == WM_MEM_HOST;
     if (n == 0) {  // (no device is touched: offsets_out[0] can only be written where the host can write it)
@@ -506,6 +564,17 @@ int cl_one(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const
     c.offsets_out = offsets_out;
     c.cap_clusters = cap_clusters;
 
+    if (cond && cond->flags) {
+        c.cond = *cond;
+        c.attr_stride = attr_stride;
+        c.attr_raw = static_cast<const unsigned char *>(attr);
+        if (attr_mem == WM_MEM_HOST) {  // uploaded first, as a host cloud is (pageable memory: a blocking copy)
+            WM_HIP(ctx, hipStreamSynchronize(st));
+            WM_HIP(ctx, w.attr_raw.reserve(n * attr_stride));
+            WM_HIP(ctx, hipMemcpy(w.attr_raw.p, attr, n * attr_stride, hipMemcpyHostToDevice));
+            c.attr_raw = w.attr_raw.as<unsigned char>();
+        }
+    }
     WM_HIP(ctx, w.sb.pts.reserve(n * sizeof(float4)));
     if (c.timed) WM_HIP(ctx, hipEventRecord(ctx->ev_a, st));
     WM_TRY(pack_cloud(ctx, pts, n, stride, mem, w.sb.pts.as<float4>()));
@@ -555,6 +624,37 @@ int wm_cluster_extract(wm_ctx *ctx, const void *pts, size_t n, size_t stride, in
     if (stats) *stats = wm_cluster_stats{};
     return cl_one(ctx, pts, n, stride, mem, p, labels_out, indices_out, cap, nullptr, 0, offsets_out, cap_clusters, out_mem,
                   n_clusters, n_out, stats, nullptr);
+}
+
+void wm_cluster_cond_default(wm_cluster_cond *c) {
+    if (c) memset(c, 0, sizeof(*c));
+}
+
+int wm_cluster_extract_cond(wm_ctx *ctx, const void *pts, size_t n, size_t stride, int mem, const void *attr, size_t attr_stride,
+                            int attr_mem, const wm_cluster_params *p, const wm_cluster_cond *c, int32_t *labels_out,
+                            int32_t *indices_out, size_t cap, uint32_t *offsets_out, size_t cap_clusters, int out_mem,
+                            size_t *n_clusters, size_t *n_out, wm_cluster_stats *stats) {
+    if (!ctx || !n_out || !n_clusters || (n > 0 && !pts) || n > 0x7FFFFFF0u || (cap > 0 && !indices_out) ||
+        (cap_clusters > 0 && !offsets_out) || !cl_args_ok(p, stride, mem, out_mem))
+        return WM_ERR_ARG;
+    if (!c || c->flags < 0 || c->flags > (WM_CLUSTER_COND_NORMAL | WM_CLUSTER_COND_SCALAR) || c->reserved != 0 ||
+        (c->flags != 0 && !attr && n > 0) || attr_stride < 16 || (attr_stride & 3) ||
+        (attr_mem != WM_MEM_HOST && attr_mem != WM_MEM_DEVICE))
+        return WM_ERR_ARG;
+    if ((c->flags & WM_CLUSTER_COND_NORMAL) &&
+        !(std::isfinite(c->max_normal_angle) && c->max_normal_angle >= 0.0 && c->max_normal_angle <= M_PI / 2))
+        return WM_ERR_ARG;
+    if ((c->flags & WM_CLUSTER_COND_SCALAR) && !(std::isfinite(c->max_scalar_diff) && c->max_scalar_diff >= 0.0))
+        return WM_ERR_ARG;
+    *n_out = 0;
+    *n_clusters = 0;
+    if (stats) *stats = wm_cluster_stats{};
+    LinkCond lc{};
+    lc.flags = c->flags;
+    if (c->flags & WM_CLUSTER_COND_NORMAL) lc.cos_min = (float) cos(c->max_normal_angle);  // (the cosine in double)
+    if (c->flags & WM_CLUSTER_COND_SCALAR) lc.max_diff = (float) c->max_scalar_diff;
+    return cl_one(ctx, pts, n, stride, mem, p, labels_out, indices_out, cap, nullptr, 0, offsets_out, cap_clusters, out_mem,
+                  n_clusters, n_out, stats, nullptr, &lc, attr, attr_stride, attr_mem);
 }
 
 int wm_cluster_extract_batch(wm_ctx *ctx, const wm_cluster_scan *scans, int n_scans, size_t stride, int mem,

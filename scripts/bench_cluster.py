@@ -16,7 +16,14 @@ beside it.  Prints one JSON line.
                      median of --rounds rounds, one entry per repeat (--repeats).  Device input, tolerance 0.2 and
                      0.5 m; the scans: the obstacle points wm_ground_segment_batch keeps from
                      rings_sensor_frame(130 000, seed 42 + k), and the 3 000-point stress shapes of the tests in turn.
-                     --skip-plain leaves the single-call part out."""
+                     --skip-plain leaves the single-call part out.
+--cond               per cloud and tolerance, in place of the plain rows: wm_cluster_extract_cond with the normal test
+                     (normals from wm_estimate_normals with k = 10 on a second context, left in device memory; angle
+                     30 degrees) beside wm_cluster_extract on the same cloud, the two alternating call by call -- device
+                     ms per call of each and their ratio -- and wm_estimate_normals alone beside them: host ms around
+                     the call on a freshly set target (the target's grid is built inside it), which ends in its own
+                     synchronise.  Under `rocprofv3 --kernel-trace --stats` the two k_cluster_link instantiations have
+                     rows of their own."""
 import argparse
 import json
 import os
@@ -41,6 +48,39 @@ def timed(ctx, cloud, calls, warmup, tolerance):
     return {"device_ms": round(float(np.median(dev)), 4), "device_ms_min_max": [round(float(min(dev)), 4), round(float(max(dev)), 4)],
             "host_ms": round(float(np.median(host)), 4), "n_finite": int(r["n_finite"]), "components": int(r["n_components"]),
             "clusters": int(r["n_clusters"]), "largest": int(r["largest"])}
+
+
+def timed_cond(ctx, nctx, cloud, calls, warmup, tolerance, k=10, angle_deg=30.0):
+    import torch
+    attr = torch.empty((len(cloud), 4), dtype=torch.float32, device=cloud.device)
+    normals = []
+    for i in range(min(calls, 10) + 1):
+        nctx.set_source(cloud[:1000])  # (wm_estimate_normals wants both clouds; only the target's normals are made)
+        nctx.set_target(cloud)
+        nctx.sizes()  # (the clouds' pending set-up is not the normals')
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        nctx.estimate_normals(1, k, out=attr)
+        if i:
+            normals.append((time.perf_counter() - t0) * 1e3)
+    angle = float(np.deg2rad(angle_deg))
+    for _ in range(warmup):
+        ctx.cluster_extract(cloud, tolerance=tolerance)
+        ctx.cluster_extract_cond(cloud, attr, tolerance=tolerance, max_normal_angle=angle)
+    plain, cond = [], []
+    for _ in range(calls):
+        r = ctx.cluster_extract(cloud, tolerance=tolerance)
+        plain.append(r["kernel_ms"])
+        rc = ctx.cluster_extract_cond(cloud, attr, tolerance=tolerance, max_normal_angle=angle)
+        cond.append(rc["kernel_ms"])
+
+    def cell(ms, res):
+        return {"device_ms": round(float(np.median(ms)), 4), "device_ms_min_max": [round(float(min(ms)), 4), round(float(max(ms)), 4)],
+                "components": int(res["n_components"]), "largest": int(res["largest"])}
+    return {"n_finite": int(r["n_finite"]), "normal_k": k, "max_normal_angle_deg": angle_deg, "plain": cell(plain, r),
+            "cond": cell(cond, rc), "cond_over_plain": round(float(np.median(cond) / np.median(plain)), 4),
+            "estimate_normals_host_ms": round(float(np.median(normals)), 4),
+            "estimate_normals_host_ms_min_max": [round(float(min(normals)), 4), round(float(max(normals)), 4)]}
 
 
 def bench_batch(ctx, sizes, rounds, warmup, repeats, tolerances):
@@ -97,12 +137,14 @@ def main():
     ap.add_argument("--clouds", default="scene_1m,rings_2m_obstacles")
     ap.add_argument("--tolerances", default="0.2,0.5", help="metres, comma separated (one per kernel trace keeps its rows apart)")
     ap.add_argument("--cell-div", default="", help="D[,D...]: again under option cluster_cell_div = D")
+    ap.add_argument("--cond", action="store_true", help="wm_cluster_extract_cond (normals, k = 10, 30 degrees) beside wm_cluster_extract")
     ap.add_argument("--yardstick", type=int, default=0, help="rounds of cluster_extract + radius outlier filter, for a kernel trace")
     a = ap.parse_args()
     TOLERANCES = [float(x) for x in a.tolerances.split(",") if x]
     import torch
     from libwave_amd import capi, synth
     ctx = capi.Context(0)
+    nctx = capi.Context(0) if a.cond else None  # the normals' context: a registration state of its own
 
     def obstacles():
         scan = torch.from_numpy(synth.scene_rings(2_000_000, seed=42)).to("cuda")
@@ -122,6 +164,9 @@ def main():
                     ctx.cluster_extract(cloud, tolerance=tol)
                     ctx.outlier_filter(cloud, method=1, radius=tol, min_neighbors=5, counts=True)
             row["yardstick_rounds"] = a.yardstick
+        elif a.cond:
+            for tol in TOLERANCES:
+                row["tolerance_%g" % tol] = timed_cond(ctx, nctx, cloud, a.calls, a.warmup, tol)
         else:
             for tol in TOLERANCES:
                 row["tolerance_%g" % tol] = timed(ctx, cloud, a.calls, a.warmup, tol)
@@ -135,6 +180,8 @@ def main():
     if sizes:
         out["batch"] = bench_batch(ctx, sizes, a.rounds, a.warmup, a.repeats, TOLERANCES)
     ctx.close()
+    if nctx:
+        nctx.close()
     print(json.dumps(out))
 
 
