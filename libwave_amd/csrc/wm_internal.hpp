@@ -425,6 +425,7 @@ struct wm_ctx {
     wm::DevBuf ndt_keys, ndt_keys2, ndt_vox, ndt_vkey, ndt_hkeys, ndt_hvals, ndt_dense, ndt_meanf, ndt_vsum;
     bool ndt_dense_on = false;  // dense cell -> voxel-slot table built (small lattices)
     int ndt_dense_lo[3] = {0, 0, 0}, ndt_dense_dim[3] = {0, 0, 0};
+    int ndt_lat_lo[3] = {0, 0, 0}, ndt_lat_dim[3] = {1, 1, 1};  // the voxel lattice over the target: low corner (cells), cells per axis
     bool ndt_cells4_on = false;
     wm::DevBuf ndt_cells4;
     int ndt_cus = 0;

@@ -35,10 +35,11 @@ constexpr int kNdtBlocks = 4096;  // upper bound; ctx->tune_ndt_blocks workgroup
 constexpr unsigned long long kEmptyKey = ~0ull;
 
 
-__host__ __device__ inline unsigned long long ndt_key(int i, int j, int k) {
-    return ((unsigned long long) (unsigned) (i + (1 << 20)) << 42) |
-           ((unsigned long long) (unsigned) (j + (1 << 20)) << 21) |
-           (unsigned long long) (unsigned) (k + (1 << 20));
+// A voxel's key: its cell RELATIVE TO THE LATTICE'S LOW CORNER (NdtLattice::lo), 21 bits per axis.  ndt_build_t refuses a
+// target that spans more than 2^20 voxels along an axis, so 0 <= i, j, k < 2^20 wherever the target lies: UTM eastings
+// at res 0.3 are cells beyond 2^21, and absolute cell numbers ran from one field into the next there.
+__host__ __device__ inline unsigned long long ndt_key(unsigned i, unsigned j, unsigned k) {
+    return ((unsigned long long) i << 42) | ((unsigned long long) j << 21) | (unsigned long long) k;
 }
 
 __device__ __forceinline__ unsigned ndt_hash(unsigned long long x) {
@@ -82,10 +83,10 @@ __global__ void __launch_bounds__(kBlock)
 
 __device__ __forceinline__ unsigned long long ndt_key_of_cell(unsigned long long cell, const NdtLattice &L) {
     const unsigned long long row = cell / L.nx;
-    const int a = (int) (cell - row * L.nx) + L.lo[0];
+    const unsigned a = (unsigned) (cell - row * L.nx);
     const unsigned long long lay = row / L.ny;
-    const int b = (int) (row - lay * L.ny) + L.lo[1];
-    const int c = (int) lay + L.lo[2];
+    const unsigned b = (unsigned) (row - lay * L.ny);
+    const unsigned c = (unsigned) lay;
     return ndt_key(c, b, a);  // k in the top bits
 }
 
@@ -347,17 +348,18 @@ __global__ void __launch_bounds__(kBlock)
 // look-up is then ONE 4-byte load instead of a hash and a probe sequence.
 
 __global__ void __launch_bounds__(kBlock)
-    k_ndt_dense_fill(const unsigned long long *__restrict__ vkey, unsigned nvox, NdtDense d, int *table,
+    k_ndt_dense_fill(const unsigned long long *__restrict__ vkey, unsigned nvox, NdtLattice L, NdtDense d, int *table,
                      const float4 *__restrict__ meanf, float4 *__restrict__ cells4) {
     const unsigned s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= nvox) return;
     const unsigned long long key = vkey[s];
     if (key == kEmptyKey) return;
-    // ndt_key(k, j, i): k in the top bits, 21 bits each, biased by 2^20
-    const int k = (int) ((key >> 42) & 0x1FFFFFu) - (1 << 20);
-    const int j = (int) ((key >> 21) & 0x1FFFFFu) - (1 << 20);
-    const int i = (int) (key & 0x1FFFFFu) - (1 << 20);
-    const int a = i - d.i0, b = j - d.j0, c = k - d.k0;
+    // ndt_key(k, j, i): k in the top bits, 21 bits each, relative to the lattice's low corner; the table's own corner
+    // lies its margin below that one
+    const int k = (int) ((key >> 42) & 0x1FFFFFu);
+    const int j = (int) ((key >> 21) & 0x1FFFFFu);
+    const int i = (int) (key & 0x1FFFFFu);
+    const int a = i + (L.lo[0] - d.i0), b = j + (L.lo[1] - d.j0), c = k + (L.lo[2] - d.k0);
     if (a < 0 || b < 0 || c < 0 || a >= d.nx || b >= d.ny || c >= d.nz) return;
     table[((size_t) c * d.ny + b) * d.nx + a] = (int) s;
     if (cells4) {
@@ -501,10 +503,15 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HES
                 }
             }
         } else {
+            // (the hash grid: `dense` carries the lattice itself, ndt_eval; a neighbour outside it is no voxel -- nor is
+            // any neighbour of a garbage query whose cell number saturated the int cast)
+            const long long qa = (long long) ci - dense.i0, qb = (long long) cj - dense.j0, qc = (long long) ck - dense.k0;
 #pragma unroll 1
             for (int nb = 0; nb < 27; ++nb) {
                 const int di = nb % 3 - 1, dj = (nb / 3) % 3 - 1, dk = nb / 9 - 1;
-                const unsigned long long key = ndt_key(ck + dk, cj + dj, ci + di);
+                const long long a = qa + di, b = qb + dj, c = qc + dk;
+                if (a < 0 || b < 0 || c < 0 || a >= dense.nx || b >= dense.ny || c >= dense.nz) continue;
+                const unsigned long long key = ndt_key((unsigned) c, (unsigned) b, (unsigned) a);
                 unsigned hpos = ndt_hash(key) & mask;
                 for (;;) {
                     const unsigned long long hk = hkeys[hpos];
@@ -805,7 +812,7 @@ static int ndt_build_t(wm_ctx *ctx, double res) {
         for (int d = 0; d < 3; ++d) {
             L.lo[d] = (int) floorf(bb.lo[d] * inv);
             const long long dd = (long long) floorf(bb.hi[d] * inv) - L.lo[d] + 1;
-            if (ctx->n_tgt > 0 && (dd < 1 || dd > (1ll << 20))) {  // ndt_key holds 21 bits per axis
+            if (ctx->n_tgt > 0 && (dd < 1 || dd > (1ll << 20))) {  // ndt_key: cells relative to lo[], 21 bits per axis
                 ctx->last_error = "NDT: the target spans more than 2^20 voxels along an axis";
                 return WM_ERR_ARG;
             }
@@ -814,6 +821,10 @@ static int ndt_build_t(wm_ctx *ctx, double res) {
         L.nx = dimv[0];
         L.ny = dimv[1];
         L.cells = dimv[0] * dimv[1] * dimv[2];
+        for (int d = 0; d < 3; ++d) {
+            ctx->ndt_lat_lo[d] = L.lo[d];
+            ctx->ndt_lat_dim[d] = (int) dimv[d];
+        }
     }
     unsigned key_bits = 1;
     while (key_bits < 64 && (L.cells >> key_bits) != 0ull) ++key_bits;
@@ -905,7 +916,7 @@ static int ndt_build_t(wm_ctx *ctx, double res) {
                 ctx->ndt_cells4_on = true;
             }
             hipLaunchKernelGGL(k_ndt_dense_fill, dim3((nvox + kBlock - 1) / kBlock), dim3(kBlock), 0,
-                               ctx->stream, ctx->ndt_vkey.as<unsigned long long>(), nvox, d,
+                               ctx->stream, ctx->ndt_vkey.as<unsigned long long>(), nvox, L, d,
                                ctx->ndt_dense.as<int>(), ctx->ndt_meanf.as<float4>(), cells4);
             WM_HIP(ctx, hipGetLastError());
             for (int k = 0; k < 3; ++k) {
@@ -996,7 +1007,9 @@ static double ndt_eval(NdtEval &E, const double p[6], double *grad, double *hess
     const unsigned long long *hk = ctx->ndt_hkeys.as<unsigned long long>();
     const unsigned *hv = ctx->ndt_hvals.as<unsigned>();
     const float4 *src = ctx->src_sorted.as<float4>();
-    NdtDense dense{nullptr, 0, 0, 0, 0, 0, 0};
+    // (no table: the hash grid, whose keys are cells relative to the lattice's low corner -- the lattice itself)
+    NdtDense dense{nullptr, ctx->ndt_lat_lo[0], ctx->ndt_lat_lo[1], ctx->ndt_lat_lo[2], ctx->ndt_lat_dim[0],
+                   ctx->ndt_lat_dim[1], ctx->ndt_lat_dim[2]};
     if (ctx->ndt_dense_on && ctx->tune_ndt_dense)
         dense = NdtDense{ctx->ndt_dense.as<int>(), ctx->ndt_dense_lo[0], ctx->ndt_dense_lo[1],
                          ctx->ndt_dense_lo[2], ctx->ndt_dense_dim[0], ctx->ndt_dense_dim[1],

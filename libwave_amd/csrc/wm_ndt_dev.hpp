@@ -150,8 +150,8 @@ __device__ inline bool ndt_voxel_record(unsigned count, const double *s, const d
 
 struct NdtDense {
     const int *table;  // nullptr: use the hash grid
-    int i0, j0, k0;    // lattice origin (cell indices)
-    int nx, ny, nz;
+    int i0, j0, k0;    // the table's origin (cell indices: the lattice's low corner less the margin); hash grid: the lattice's
+    int nx, ny, nz;    // the table's cells per axis (margins included); hash grid: the lattice's
 };
 
 struct __attribute__((packed, aligned(4))) Int3 {  // three adjacent table cells, one 12-byte load
