@@ -72,13 +72,23 @@ __device__ double g_knn_cnt[8];  // candidates, wave trips, batches (per lane), 
 // elsewhere, four rows (eight segments) per batch -- and of the shell only the rows the sphere of the k-th distance
 // found so far can reach.  (Re-scanning the whole bigger box was 75 candidates through the sorted insertion per
 // query instead of ~45; the insertion -- K compare-swaps for the whole wave per candidate -- is 85 % of k_gicp_cov.)
-template <int K>
+// OUTSIDE: the query is a point of ANOTHER cloud (the batch's correspondence search) and may lie any number of cells
+// outside the grid -- 5 cm from a cloud whose cells are 16 um, all its points being one: the radius that covers the
+// whole grid is then counted from where the query is.  (Capped at the grid's own size, the box of such a query never
+// reached the grid, and the search came back empty-handed after its 64 passes.)  The distance is a float count of
+// cells: beyond ~2^24 cells its rounding exceeds the three cells of slack in rmax and the box at r == rmax may not
+// test as covering the grid -- the caller's r_stop (a box margin of max_corr) ends such a search first, with
+// everything within r_stop seen, unless a cell is smaller than max_corr / 2^24.
+template <int K, bool OUTSIDE = false>
 __device__ void knn_search(const GridDev &g, float qx, float qy, float qz, int k, float r0_cells,
                            unsigned long long (&best)[K], uint2 *runs, unsigned lane_col, unsigned col_stride,
                            float r_stop = 3.0e38f) {
     const float fx = (qx - g.ox) * g.inv_h, fy = (qy - g.oy) * g.inv_h, fz = (qz - g.oz) * g.inv_h;
     float r = r0_cells * g.h;
-    const float rmax = (float) (g.nx + g.ny + g.nz + 3) * g.h;  // covers the whole grid
+    float outside = 0.f;  // cells between the query and the grid, along the axis where that is most
+    if constexpr (OUTSIDE)
+        outside = fmaxf(fmaxf(fmaxf(-fx, fx - (float) g.nx), fmaxf(-fy, fy - (float) g.ny)), fmaxf(fmaxf(-fz, fz - (float) g.nz), 0.f));
+    const float rmax = ((float) (g.nx + g.ny + g.nz + 3) + outside) * g.h;  // covers the whole grid
 #pragma unroll
     for (int j = 0; j < K; ++j) best[j] = ~0ull;
     // the runs of one batch (s >= e: none) -> the lane's column of the LDS list -> ONE flat candidate loop

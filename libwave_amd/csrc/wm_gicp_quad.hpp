@@ -13,8 +13,16 @@
 // with A_(ac)(jk) = sum M_ac z_j z_k (6 x 10 by symmetry), B0_aj = sum (M r0)_a z_j (12), C0 = sum r0^T M r0 and the
 // pair count: 74 sums, formed ONCE per outer iteration (k_gicp_quad, wm_gicp.hip; gs_statistics, wm_gicp_small.hip).
 // f, the translation gradient (G's last column) and PCL's rotation accumulator (sum p_base (M r)^T = B G^T) follow
-// for any x without touching the pairs again.  The expansion is around T0, where the optimiser starts: D is small,
-// nothing cancels (the constant term IS the objective at the starting point).
+// for any x without touching the pairs again.  The expansion is around T0, where the optimiser starts: D is small and
+// the constant term IS the objective at the starting point.  How far it is from the same function evaluated pair by
+// pair in long double (tests/test_gicp_reference_cpu.py, on clouds next to the origin and 55 km from it): a few units in
+// the last place of f and of the gradient -- at T0, after a translation-only step of a centimetre, and after a further
+// 1e-4 rad per axis.  There the rotation entries of D are 5e-9 (1 - cos) to 1e-4 where the translation entries are 0.01,
+// and they multiply A, the sum M z z^T block, which is |z|^2 times larger than B0; but A's entries are correctly rounded
+// sums, so what A contributes, D A D, carries a relative 1e-16 of ITSELF, and it is of f's own size at the most unless
+// the step takes the residuals to zero (f >= (sqrt(C0) - sqrt(D A D))^2).  (What does cost 1e-8 of f at such a step is
+// one ulp in an entry of the float matrix T(x): a comparison has to form T(x) as applyState does -- float sines and
+// cosines, float products --, not by rounding a double matrix.)
 //
 // What is kept of PCL's arithmetic: r0 is PCL's residual -- the float transform, the float subtraction -- so at
 // x = x0 the value is the one PCL computes, and T(x) is PCL's float matrix (applyState).  What is not: away from x0

@@ -463,7 +463,7 @@ __device__ __attribute__((noinline)) void gs_correspondences(GsShared &S, uint2 
         xform_pcl(T, p.x, p.y, p.z, qx, qy, qz);
         unsigned long long best[1];
         if (debug & 4) best[0] = i < n_t ? (unsigned long long) __float_as_uint(gt.pts[i].w) : ~0ull;  // (developer timing experiment: no search)
-        else knn_search<1>(gt, qx, qy, qz, 1, 0.5f, best, runs, tid, kGsThreads, r_stop);
+        else knn_search<1, true>(gt, qx, qy, qz, 1, 0.5f, best, runs, tid, kGsThreads, r_stop);
         unsigned j = kNoIdx;
         if (best[0] != ~0ull && __uint_as_float((unsigned) (best[0] >> 32)) <= thr_d2) j = (unsigned) best[0];
         match[i] = j;

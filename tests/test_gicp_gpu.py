@@ -1,6 +1,8 @@
 """GPU parity of the GICP path (k-NN covariances, Mahalanobis matrices, objective /
 gradient reduction, BFGS driver) vs the oracle, on the reference's own test cases
-(wave_matching/tests/gicp_tests.cpp:43-100)."""
+(wave_matching/tests/gicp_tests.cpp:43-100).
+The same path on stress cases, against the oracle and a numpy reference: tests/test_gicp_stress_gpu.py (cases and
+reference: tests/gicp_reference.py, itself checked by tests/test_gicp_reference_cpu.py)."""
 import numpy as np
 import pytest
 
