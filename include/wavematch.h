@@ -1158,6 +1158,76 @@ int wm_cluster_boxes(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes
                      const uint32_t *offsets, size_t n_clusters, int list_mem,
                      wm_cluster_box *boxes_out, int out_mem, float *kernel_ms /* NULL ok */);
 
+/* ------------------------------------------------------------- feature descriptors */
+/* pcl::FPFHEstimation with a k-neighbourhood (setKSearch) and the nearest-descriptor correspondences of
+ * pcl::registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33> (determineCorrespondences and
+ * determineReciprocalCorrespondences) on the device: what a coarse alignment without an initial pose starts from.
+ * [PCL-upstream: restated from PCL 1.8 features/impl/fpfh.hpp and features/impl/pfh_tools.hpp (computePairFeatures);
+ * PCL is not linked; tests/fpfh_reference.py is the checker.]
+ *
+ * All arithmetic is IEEE float32, every operation rounded, nothing fused, in the order written.  A dot product is
+ * (x x' + y y') + z z'; a cross-product component is a b - c d; a norm is sqrtf of the dot product; pi is
+ * 3.14159274f and 1 / (2 pi) is 0.159154937f.  Everything but atan2f is therefore reproducible bit for bit.
+ *   neighbourhood  N(p) = the feature_k nearest points of p's own cloud, p included: the lists of wm_debug_knn (float d2,
+ *                  ascending by (d2, index)).  A neighbour with d2 == 0 (p itself, an exact duplicate) is skipped in
+ *                  both passes: PCL's `f4 == 0` in the first and `dists == 0` in the second.
+ *   pair (p, q)    n_p, n_q: the points' normals, the first three floats of their wm_estimate_normals records or of the
+ *                  caller's.  dp = q - p; f4 = |dp|; a1 = (n_p . dp) / f4; a2 = (n_q . dp) / f4.  If fabsf(a1) <
+ *                  fabsf(a2) (PCL's acos(fabs(a1)) > acos(fabs(a2))): (n1, n2, dp, f3) = (n_q, n_p, -dp, -a2), else
+ *                  (n_p, n_q, dp, a1).  v = dp x n1; |v| == 0: the pair is skipped; v = v / |v| (three divisions).
+ *                  w = n1 x v; f2 = v . n2; f1 = atan2f(w . n2, n1 . n2).  A pair with a (0, 0, 0) normal is skipped.
+ *   SPFH(p)        three histograms of 11 integer counts; each pair (p, q), q in N(p), that is not skipped adds one to
+ *                  bin floorf(11 * ((f1 + pi) * (1 / (2 pi)))) of the first, floorf(11 * ((f2 + 1) * 0.5f)) of the
+ *                  second, floorf(11 * ((f3 + 1) * 0.5f)) of the third, each clamped to 0 ... 10.  (PCL adds
+ *                  100 / (k - 1) per pair; the factor cancels below.)
+ *   FPFH(p)        per block, acc[b] += (float) count_q[b] * (1.0f / d2(p, q)) over q in N(p) in list order (p's own
+ *                  SPFH is not added, as in PCL); scale = 100.0f / sum_b acc[b], the sum in bin order, 0 when the sum
+ *                  is 0; out[b] = acc[b] * scale.  33 floats per input point in the caller's order: f1's block, f2's,
+ *                  f3's.  A non-finite point and a point whose own normal is (0, 0, 0) give 33 zeros (PCL: NaN).
+ *   match          d2(i, j) = sum over b = 0 ... 32 of (A[i][b] - B[j][b])^2, accumulated in bin order.  The match of
+ *                  row i of A is the row j of B with the smallest (d2, j).  A row of 33 zeros has no match and is
+ *                  nobody's match.  Reciprocal: i keeps j only if i is the match of j among A's rows, else -1.  Rows
+ *                  must be finite. */
+typedef struct {
+    int normal_k;   /* neighbours of a normal (normals_in == NULL), 3 ... 32; 0: the default, 10 */
+    int feature_k;  /* neighbours of a descriptor, the point itself included, 3 ... 32; 0: the default, 10 */
+} wm_fpfh_params;
+typedef struct {
+    size_t n_valid;    /* finite points whose own normal is not (0, 0, 0): the rows that are not zero by rule */
+    float normals_ms;  /* device time of the normals (0 when given or reused) */
+    float spfh_ms;     /* ... of the first pass: search, pair features, counts, lists */
+    float weight_ms;   /* ... of the second pass: the weighted sums and their scaling */
+} wm_fpfh_stats;
+void wm_fpfh_default_params(wm_fpfh_params *p);  /* normal_k 10, feature_k 10 */
+
+/* The descriptors of the context's source (which = 0) or target (which = 1), as wm_estimate_normals addresses them.
+ * normals_in: NULL = the normals wm_estimate_normals(which, normal_k) gives (the target's are reused when the context
+ * holds them for that k, and stay on it); otherwise float x 4 per input point in the caller's order (the fourth float
+ * is not read), in `out_mem`'s memory space: PCL's setInputNormals.  fpfh_out: n x 33 floats; spfh_out (NULL ok):
+ * n x 33 unsigned char, the first pass's counts in the caller's order, for tests and developers; both in `out_mem`.
+ * WM_ERR_ARG: a null ctx or fpfh_out, a k outside 3 ... 32, a bad `which` or `out_mem`.  WM_ERR_STATE without both
+ * clouds.  WM_NOT_CONVERGED when the cloud has fewer than feature_k (normals_in == NULL: or normal_k) finite points;
+ * nothing is written then.  The workspace is the context's own (freed by wm_ctx_destroy). */
+int wm_fpfh_estimate(wm_ctx *ctx, int which, const wm_fpfh_params *params /* NULL: the defaults */,
+                     const void *normals_in /* NULL ok */, float *fpfh_out, uint8_t *spfh_out /* NULL ok */, int out_mem,
+                     wm_fpfh_stats *stats /* NULL ok */);
+
+#define WM_FEATURE_DIM 33
+#define WM_FEATURE_MAX_ROWS (1u << 20)
+typedef struct {
+    size_t n_matched;  /* rows of A with a match (after the reciprocal test) */
+    float kernel_ms;   /* device time from the rows' arrival to the last output */
+} wm_feature_match_stats;
+/* For every one of `na` rows of A its match among the `nb` rows of B (the rule above).  A row is 33 floats at the head
+ * of a record of a_stride_bytes / b_stride_bytes (>= 132, a multiple of 4); both arrays in `mem`.  idx_out: int32 x na,
+ * d2_out: float x na (NULL ok), in `out_mem`; a row without a match gets -1 and 0.  na, nb <= WM_FEATURE_MAX_ROWS;
+ * nb == 0: no row has a match.  Argument errors (a null ctx or idx_out, a null array with rows, a bad stride, mem or
+ * out_mem, too many rows) are found before a device is touched; na == 0: WM_OK with no device touched.  The call needs
+ * no clouds on the context and touches no registration state. */
+int wm_feature_match(wm_ctx *ctx, const void *a, size_t na, size_t a_stride_bytes, const void *b, size_t nb,
+                     size_t b_stride_bytes, int mem, int reciprocal, int32_t *idx_out, float *d2_out /* NULL ok */,
+                     int out_mem, wm_feature_match_stats *stats /* NULL ok */);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

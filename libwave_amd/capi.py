@@ -209,6 +209,22 @@ WM_SAC_BATCH_MAX_POINTS = 0x7FFFFFF0  # the points of a sac_segment_batch's scan
 WM_SAC_BATCH_MAX_SCANS = 0x1000000
 
 
+class FpfhParams(C.Structure):
+    _fields_ = [("normal_k", C.c_int), ("feature_k", C.c_int)]
+
+
+class FpfhStats(C.Structure):
+    _fields_ = [("n_valid", C.c_size_t), ("normals_ms", C.c_float), ("spfh_ms", C.c_float), ("weight_ms", C.c_float)]
+
+
+class FeatureMatchStats(C.Structure):
+    _fields_ = [("n_matched", C.c_size_t), ("kernel_ms", C.c_float)]
+
+
+WM_FEATURE_DIM = 33
+WM_FEATURE_MAX_ROWS = 1 << 20  # rows per side of a feature_match
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -386,6 +402,12 @@ def lib():
                                            C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_int),
                                            C.POINTER(SacStats), C.POINTER(C.c_float)]
+        L.wm_fpfh_default_params.argtypes = [C.POINTER(FpfhParams)]
+        L.wm_fpfh_default_params.restype = None
+        L.wm_fpfh_estimate.argtypes = [C.c_void_p, C.c_int, C.POINTER(FpfhParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.POINTER(FpfhStats)]
+        L.wm_feature_match.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(FeatureMatchStats)]
         _LIB = L
     return _LIB
 
@@ -454,6 +476,30 @@ def outlier_params(params=None, **kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def fpfh_params(params=None, **kw):
+    """wm_fpfh_params from the defaults (wm_fpfh_default_params: both k 10), a dict of field values and keywords."""
+    p = FpfhParams()
+    lib().wm_fpfh_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _rows_arg(a):
+    """-> (pointer, n, stride, mem, keepalive) of descriptor rows: float32 (n, >= 33) numpy array or torch tensor, the
+    33 floats at the head of each row."""
+    if isinstance(a, np.ndarray):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        assert a.ndim == 2 and a.shape[1] >= WM_FEATURE_DIM
+        return a.ctypes.data, a.shape[0], a.shape[1] * 4, WM_MEM_HOST, a
+    import torch
+    assert isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.dim() == 2 and a.shape[1] >= WM_FEATURE_DIM
+    a = a.contiguous()
+    return a.data_ptr(), a.shape[0], a.shape[1] * 4, WM_MEM_DEVICE if a.is_cuda else WM_MEM_HOST, a
 
 
 def cluster_params(params=None, **kw):
@@ -1309,6 +1355,64 @@ class Context:
         self._check(lib().wm_estimate_normals(self._h, int(which), int(k), C.c_void_p(out.data_ptr()), WM_MEM_DEVICE),
                     "wm_estimate_normals")
         return out
+
+    # ---- feature descriptors
+    def fpfh(self, which=1, normals=None, counts=False, out=None, **kw):
+        """pcl::FPFHEstimation with a k-neighbourhood (wm_fpfh_estimate) on the target (which = 1) or the source (0) ->
+        dict: rc, fpfh (n, 33) float32 in the caller's order, counts (n, 33) uint8 (the first pass's SPFH counts; None
+        without counts=True) and the fields of wm_fpfh_stats.  normals: None (estimated with normal_k) or (n, 4) float32,
+        PCL's setInputNormals.  out: a float32 CUDA tensor (n, 33) to fill on the device -- then `normals` must be a
+        CUDA tensor too and counts comes back as one; None: numpy arrays.  Keywords: normal_k, feature_k.  rc: WM_OK or
+        WM_NOT_CONVERGED (fewer finite points than a k: the arrays are None)."""
+        n = self.n_tgt if which == 1 else self.n_src
+        p = fpfh_params(**kw)
+        st = FpfhStats()
+        if out is None:
+            mem = WM_MEM_HOST
+            res = np.zeros((n, WM_FEATURE_DIM), np.float32)
+            cnt = np.zeros((n, WM_FEATURE_DIM), np.uint8) if counts else None
+            if normals is not None:
+                normals = np.ascontiguousarray(normals, dtype=np.float32)
+                assert normals.shape == (n, 4)
+            addr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+        else:
+            import torch
+            mem = WM_MEM_DEVICE
+            assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, WM_FEATURE_DIM) and out.dtype == torch.float32
+            res = out
+            cnt = torch.zeros((n, WM_FEATURE_DIM), dtype=torch.uint8, device=out.device) if counts else None
+            if normals is not None:
+                assert normals.is_cuda and normals.dtype == torch.float32 and tuple(normals.shape) == (n, 4)
+                normals = normals.contiguous()
+            torch.cuda.synchronize(out.device)  # (the library works on a stream of its own)
+            addr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
+        rc = self._check(lib().wm_fpfh_estimate(self._h, int(which), C.byref(p), addr(normals), addr(res), addr(cnt), mem,
+                                                C.byref(st)), "wm_fpfh_estimate")
+        d = dict(rc=rc, fpfh=res if rc == WM_OK else None, counts=cnt if rc == WM_OK else None)
+        d.update({k: getattr(st, k) for k, _ in FpfhStats._fields_})
+        return d
+
+    def feature_match(self, a, b, reciprocal=False):
+        """Nearest-descriptor correspondences (wm_feature_match) -> dict: idx (na,) int32 (the row of b matched to each
+        row of a; -1: none), d2 (na,) float32, n_matched, kernel_ms.  a, b: float32 (n, >= 33) numpy arrays or torch
+        tensors of one kind, the 33 floats at the head of each row; outputs live where the rows live."""
+        pa, na, sa, mem, keep_a = _rows_arg(a)
+        pb, nb, sb, mem_b, keep_b = _rows_arg(b)
+        assert mem == mem_b
+        st = FeatureMatchStats()
+        if mem == WM_MEM_DEVICE:
+            import torch
+            idx = torch.full((max(na, 1),), -1, dtype=torch.int32, device=a.device)
+            d2 = torch.zeros(max(na, 1), dtype=torch.float32, device=a.device)
+            torch.cuda.synchronize(a.device)
+            pi, pd = idx.data_ptr(), d2.data_ptr()
+        else:
+            idx = np.full(max(na, 1), -1, np.int32)
+            d2 = np.zeros(max(na, 1), np.float32)
+            pi, pd = idx.ctypes.data, d2.ctypes.data
+        self._check(lib().wm_feature_match(self._h, C.c_void_p(pa), na, sa, C.c_void_p(pb), nb, sb, mem, int(bool(reciprocal)),
+                                           C.c_void_p(pi), C.c_void_p(pd), mem, C.byref(st)), "wm_feature_match")
+        return dict(idx=idx[:na], d2=d2[:na], n_matched=st.n_matched, kernel_ms=st.kernel_ms)
 
     # ---- NDT
     def ndt_align(self, params=None, **kw):

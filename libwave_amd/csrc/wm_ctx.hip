@@ -330,6 +330,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     cluster_release(ctx);
     sac_release(ctx);
     boxes_release(ctx);
+    fpfh_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

@@ -348,6 +348,7 @@ struct wm_ctx {
     void *cluster = nullptr;                // wm_cluster.hip: the cluster extraction's workspace (its own as well)
     void *sac = nullptr;                    // wm_sac.hip: the plane segmentation's workspace (its own as well)
     void *boxes = nullptr;                  // wm_describe.hip: the cluster boxes' workspace (its own as well)
+    void *fpfh = nullptr;                   // wm_fpfh.hip, wm_feature_match.hip: the descriptors' workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -668,10 +669,15 @@ void sac_release(wm_ctx *ctx);
 // ---- wm_describe.hip
 void boxes_release(wm_ctx *ctx);
 
+// ---- wm_fpfh.hip (the workspace both descriptor files share; wm_feature_match.hip's part is released with it)
+void fpfh_release(wm_ctx *ctx);
+
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0
 int plane_normal_k(int k);          // 0 -> the default
 int plane_target_normals(wm_ctx *ctx, int k);  // the target's normals on the context (cached per target and k)
+// the source's on ctx->plane_nrm_src (its grid stays on ctx->src_grid); k resolved
+int plane_source_normals(wm_ctx *ctx, int k, bool grid_ready = false);
 int plane_bins_ready(wm_ctx *ctx);
 int launch_plane_stats(wm_ctx *ctx, const int *rej = nullptr);  // after a search-only launch: the 29 sums into the plane bins
 int launch_plane_solve(wm_ctx *ctx, unsigned long long *pub, int pub_slots, int solve);  // solve == 0: the sums into st->stats only

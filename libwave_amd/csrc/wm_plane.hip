@@ -127,6 +127,19 @@ int plane_target_normals(wm_ctx *ctx, int k) {
     return WM_OK;
 }
 
+// the source's normals (caller order) into ctx->plane_nrm_src, over the source's own grid (left built on ctx->src_grid);
+// k is already resolved (plane_normal_k or the caller's own default); grid_ready: the caller has just built that grid
+int plane_source_normals(wm_ctx *ctx, int k, bool grid_ready) {
+    if (k < 3 || k > 32) return WM_ERR_ARG;
+    if ((size_t) k > ctx->n_src) return WM_NOT_CONVERGED;
+    const size_t n_out = ctx->n_src_input;
+    WM_HIP(ctx, ctx->plane_nrm_src.reserve((n_out + 1) * sizeof(float4)));
+    WM_HIP(ctx, hipMemsetAsync(ctx->plane_nrm_src.p, 0, n_out * sizeof(float4), ctx->stream));
+    if (!grid_ready) WM_TRY(source_grid(ctx));  // wm_gicp.hip: the grid over the source that its covariances search
+    return launch_normals_k(ctx, ctx->src_grid.d, ctx->src_sorted.as<float4>(), ctx->n_src, ctx->src_orig.as<float4>(), n_out, k,
+                            ctx->plane_nrm_src.as<float4>());
+}
+
 // ------------------------------------------------------------------ the plane sums
 // The 29 sums in the public GN layout (kGnN, kGnSd2, kGnH, kGnG).  A streaming kernel: per query 16 B of source point,
 // 8 B of key, 16 B of matched point and one 16-B gather of the match's normal out of a table the cache holds (16 MB at
@@ -335,13 +348,8 @@ extern "C" int wm_estimate_normals(wm_ctx *ctx, int which, int k, void *normals_
         res = ctx->plane_nrm.as<float4>();
         n_out = ctx->n_tgt_input;
     } else {
-        if ((size_t) k > ctx->n_src) return WM_NOT_CONVERGED;
+        WM_TRY(plane_source_normals(ctx, k));
         n_out = ctx->n_src_input;
-        WM_HIP(ctx, ctx->plane_nrm_src.reserve((n_out + 1) * sizeof(float4)));
-        WM_HIP(ctx, hipMemsetAsync(ctx->plane_nrm_src.p, 0, n_out * sizeof(float4), ctx->stream));
-        WM_TRY(source_grid(ctx));  // wm_gicp.hip: the grid over the source that its covariances search
-        WM_TRY(launch_normals_k(ctx, ctx->src_grid.d, ctx->src_sorted.as<float4>(), ctx->n_src, ctx->src_orig.as<float4>(), n_out, k,
-                                ctx->plane_nrm_src.as<float4>()));
         res = ctx->plane_nrm_src.as<float4>();
     }
     if (out_mem == WM_MEM_DEVICE) {
