@@ -316,6 +316,15 @@ int wm_debug_sort_pairs(wm_ctx *ctx, const void *keys, int key_bytes, size_t n, 
  * WM_NOT_CONVERGED when the cloud has fewer than k finite points, WM_ERR_STATE without both clouds.  Cached covariances,
  * normals and tuned cell sizes stay as they were. */
 int wm_debug_knn(wm_ctx *ctx, int which, int k, int32_t *idx_out, float *d2_out);
+/* Developer / tests, synchronous: one level of the target's search grid as the search kernels read it.  max_corr > 0:
+ * the ladder for that radius is built first if it is not there (no source needed); otherwise the level must exist
+ * (WM_ERR_STATE).  geom[5] = origin x y z, cell size h, 1 / h; dims[3] = nx ny nz; *n_points = the points the level
+ * holds (the finite ones).  cell_start (HOST, may be NULL): nx * ny * nz + 1 words when cell_cap holds them; pts (HOST,
+ * may be NULL): *n_points + 4 entries of four floats (x y z, the original index's bits) -- the cell-sorted array and the
+ * four pad entries behind it -- when pts_cap (in entries) holds them.  WM_ERR_ARG when a given buffer is too small
+ * (geom, dims and *n_points are filled all the same: call once without buffers for the sizes). */
+int wm_debug_grid_level(wm_ctx *ctx, int level, double max_corr, float geom[5], int dims[3], size_t *n_points,
+                        unsigned *cell_start, size_t cell_cap, float *pts, size_t pts_cap);
 /* Tuning knobs by name (tests, benchmarks; the defaults are the product's).  Each is also read from the environment
  * when a context is created (mostly WM_TUNE_<NAME>; INTEGRATION.md lists them all).  Among them: "cert_from"
  * (-1: the certificate kernel takes over once an ICP step is small, -2: never, k >= 0: from iteration k of every

@@ -347,6 +347,8 @@ def lib():
         L.wm_debug_solve_cycles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.wm_debug_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint, C.c_void_p]
         L.wm_debug_knn.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _fp]
+        L.wm_debug_grid_level.argtypes = [C.c_void_p, C.c_int, C.c_double, _fp, _ip, C.POINTER(C.c_size_t), C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_size_t]
         L.wm_debug_cost_log.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.wm_debug_phase_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.wm_get_correspondences.argtypes = [C.c_void_p, _ip, _fp, C.c_size_t]
@@ -1574,6 +1576,24 @@ class Context:
         if rc != WM_OK:
             raise WmError("wm_debug_knn: %s" % lib().wm_strerror(rc).decode())
         return idx, d2
+
+    def debug_grid_level(self, level, max_corr=0.0):
+        """wm_debug_grid_level: level `level` of the target's search grid as the search kernels read it (max_corr > 0:
+        the ladder for that radius is built first) -> dict(origin [3] f32, h, inv_h (f32), dims (nx, ny, nz),
+        cell_start [ncells + 1] uint32, pts [n + 4, 4] f32: the cell-sorted points, .w = the original index's bits, and
+        the four pad entries)."""
+        geom = np.zeros(5, np.float32)
+        dims = np.zeros(3, np.int32)
+        n = C.c_size_t(0)
+        args = (self._h, int(level), float(max_corr), geom.ctypes.data_as(_fp), dims.ctypes.data_as(_ip), C.byref(n))
+        self._check(lib().wm_debug_grid_level(*args, None, 0, None, 0), "wm_debug_grid_level")
+        ncells = int(dims[0]) * int(dims[1]) * int(dims[2])
+        cell_start = np.zeros(ncells + 1, np.uint32)
+        pts = np.zeros((n.value + 4, 4), np.float32)
+        self._check(lib().wm_debug_grid_level(*args, cell_start.ctypes.data, cell_start.size, pts.ctypes.data, pts.shape[0]),
+                    "wm_debug_grid_level")
+        return dict(origin=geom[:3].copy(), h=geom[3], inv_h=geom[4], dims=tuple(int(d) for d in dims),
+                    cell_start=cell_start, pts=pts)
 
     def solve_cycles(self):
         buf = (C.c_uint64 * 8)()

@@ -239,6 +239,8 @@ const Option kOptions[] = {
     {"sac_round", "WM_TUNE_SAC_ROUND", &wm_ctx::tune_sac_round, nullptr, 1, 1024, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
+    // the grids' counting sort (wm_grid.hip)
+    {"grid_rows", "WM_TUNE_GRID_ROWS", &wm_ctx::tune_grid_rows, nullptr, 0, 2, 0},
     {"ndt_dense", "WM_TUNE_NDT_DENSE", &wm_ctx::tune_ndt_dense, nullptr, kIntMin, kIntMax, 0},
     {"ndt_vox_split", "WM_TUNE_NDT_VOX_SPLIT", &wm_ctx::tune_ndt_vox_split, nullptr, kIntMin, kIntMax, kNdtModel},
     {"ndt_keys64", "WM_TUNE_NDT_KEYS64", &wm_ctx::tune_ndt_keys64, nullptr, kIntMin, kIntMax, kFlag | kNdtModel},
@@ -319,7 +321,8 @@ void wm_ctx_destroy(wm_ctx *ctx) {
                       &ctx->partials, &ctx->partials2, &ctx->bins, &ctx->nn_bound, &ctx->late_ctl, &ctx->cert_count, &ctx->cert_prof, &ctx->cost_log, &ctx->phase_log, &ctx->shard_ref, &ctx->shard_tgt,
                       &ctx->shard_ref_band, &ctx->shard_tgt_band, &ctx->shard_misc, &ctx->shard_flags, &ctx->shard_pos_t,
                       &ctx->shard_pos_s, &ctx->shard_stats, &ctx->ndt_sum_dev, &ctx->corr_tmp_idx, &ctx->corr_tmp_d2, &ctx->d_state,
-                      &ctx->plane_nrm, &ctx->plane_nrm_src, &ctx->plane_bins, &ctx->reject_buf, &ctx->reject_tmp};
+                      &ctx->plane_nrm, &ctx->plane_nrm_src, &ctx->plane_bins, &ctx->reject_buf, &ctx->reject_tmp,
+                      &ctx->row_hist, &ctx->row_tmp};
     for (DevBuf *b : bufs) b->release();
     ctx->icp_stage.release();
     ctx->gicp_stage.release();

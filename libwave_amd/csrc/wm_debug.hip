@@ -168,6 +168,28 @@ int wm_debug_cert_prof(wm_ctx *ctx, unsigned long long *out, int cap) {
     return n;
 }
 
+int wm_debug_grid_level(wm_ctx *ctx, int level, double max_corr, float geom[5], int dims[3], size_t *n_points,
+                        unsigned *cell_start, size_t cell_cap, float *pts, size_t pts_cap) {
+    if (!ctx || level < 0 || level >= kMaxLevels || !geom || !dims || !n_points) return WM_ERR_ARG;
+    if (ctx->n_tgt_input == 0) return WM_ERR_STATE;
+    WM_HIP(ctx, hipSetDevice(ctx->device));
+    if (max_corr > 0) {
+        WM_TRY(finalize_clouds(ctx));
+        WM_TRY(ensure_levels(ctx, max_corr));
+    }
+    if (level >= ctx->n_levels || !ctx->levels[level].built) return WM_ERR_STATE;
+    const GridLevel &l = ctx->levels[level];
+    geom[0] = l.d.ox, geom[1] = l.d.oy, geom[2] = l.d.oz, geom[3] = l.d.h, geom[4] = l.d.inv_h;
+    dims[0] = l.d.nx, dims[1] = l.d.ny, dims[2] = l.d.nz;
+    unsigned total = 0;
+    WM_TRY(copy_to_caller(ctx, &total, l.cell_start.as<unsigned>() + l.ncells, sizeof(unsigned)));
+    *n_points = total;
+    if ((cell_start && cell_cap < l.ncells + 1) || (pts && pts_cap < (size_t) total + 4)) return WM_ERR_ARG;
+    if (cell_start) WM_TRY(copy_to_caller(ctx, cell_start, l.cell_start.p, (l.ncells + 1) * sizeof(unsigned)));
+    if (pts) WM_TRY(copy_to_caller(ctx, pts, l.pts.p, ((size_t) total + 4) * sizeof(float4)));
+    return WM_OK;
+}
+
 int wm_get_iteration_times(wm_ctx *ctx, float *nn_ms, int cap) {
     if (!ctx || !nn_ms || cap < 0) return 0;
     int n = (int) ctx->iter_nn_ms.size();

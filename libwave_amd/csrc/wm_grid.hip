@@ -2,7 +2,8 @@
 // kd-tree (pcl::Registration::initCompute -> KdTreeFLANN::setInputCloud, triggered
 // by icp.align at wave_matching/src/icp.cpp:95,116,126):
 //   pack (AoS stride -> float4 + index, non-finite filter)  -> bbox reduction
-//   -> cell histogram -> exclusive scan -> scatter (counting sort by cell)
+//   -> cell histogram -> exclusive scan -> scatter (counting sort by cell), or, on a large lattice, the same tables
+//   band of rows by band of rows (counting_sort_rows; rows_apply says where)
 // Target levels are sorted x-fastest so that x-adjacent cells are contiguous in
 // memory; the source cloud is counting-sorted by a Morton cell code so that a
 // wavefront's 64 consecutive queries stay spatially compact under any rigid T.
@@ -236,14 +237,23 @@ int compute_bbox(wm_ctx *ctx, const float4 *pts, size_t n, Bbox *out, size_t *n_
 struct LinearKey {  // x-fastest dense cell index (target levels)
     float ox, oy, oz, inv_h;
     int nx, ny, nz;
+    // THE cell of a point: every kernel that needs it (the counting sorts, k_coarse_move) asks here
+    __device__ void cell(const float4 &p, int *cx, int *cy, int *cz) const {
+        *cx = min(max((int) floorf((p.x - ox) * inv_h), 0), nx - 1);
+        *cy = min(max((int) floorf((p.y - oy) * inv_h), 0), ny - 1);
+        *cz = min(max((int) floorf((p.z - oz) * inv_h), 0), nz - 1);
+    }
+    // ... as its (y, z) row and its place along x: the cell index is row * nx + cx
+    __device__ void row_x(const float4 &p, unsigned *row, unsigned *cx) const {
+        int x, y, z;
+        cell(p, &x, &y, &z);
+        *row = (unsigned) (z * ny + y);
+        *cx = (unsigned) x;
+    }
     __device__ unsigned operator()(const float4 &p) const {
-        int cx = (int) floorf((p.x - ox) * inv_h);
-        int cy = (int) floorf((p.y - oy) * inv_h);
-        int cz = (int) floorf((p.z - oz) * inv_h);
-        cx = min(max(cx, 0), nx - 1);
-        cy = min(max(cy, 0), ny - 1);
-        cz = min(max(cz, 0), nz - 1);
-        return (unsigned) ((cz * ny + cy) * nx + cx);
+        unsigned row, cx;
+        row_x(p, &row, &cx);
+        return row * (unsigned) nx + cx;
     }
 };
 
@@ -354,6 +364,216 @@ static int counting_sort(wm_ctx *ctx, const float4 *pts, size_t n, KeyFn key, si
     return WM_OK;
 }
 
+// ------------------------------------------- counting sort by cell, row by row
+// A level is ordered by cell index row * nx + cx, so a (y, z) ROW of cells is one contiguous run of the point array and
+// of cell_start.  On a large lattice only a few per cent of the cells hold a point, and the sort above pays for every
+// cell three times (the memset, the scan's read, the scan's write) and for a returning atomic per point scattered over
+// the whole table.  By rows every cell costs one store and no atomic leaves a compute unit: the points are first put
+// in order of their BAND -- 2^k consecutive rows, few enough that a counter per cell of the band fits a workgroup's
+// LDS --, then a workgroup per band counts its points per cell in LDS, scans the counters there and writes the band's
+// stretch of cell_start and the points' final places.  The order by band is one pass of a radix sort with a band per
+// digit (wm_sort.hpp, whose scan it uses), its tiles' ranks taken in LDS.  Four launches:
+//   k_rows_hist     per tile of 4 096 points: how many fall in each band        -> hist[band][tile]
+//   k_rs_scan       a workgroup per band: its tiles' counts -> their exclusive prefix, the band's total
+//   k_rows_scatter  the bands' first slots (a scan of the totals, in LDS, by every tile; tile 0 leaves it for the last
+//                   kernel), then the tile's points to band start + prefix + rank in the tile, into a temporary
+//   k_rows_finish   cell_start and the level's point array
+// (Counters per row in device memory, a returning atomic each, were tried first: atomics run at the memory side, and a
+// million of them on the 80 KB table of a 1M-point level took 85 us, against 48 us for k_count's over its 56 MB.)
+// The order inside a cell is the atomics' arrival order, as above; cell_start is the same table.
+constexpr int kRowThreads = 512;              // of all three kernels
+constexpr int kRowTile = kRowThreads * 8;     // points per tile
+constexpr unsigned kRowNxCap = 4000;          // cells along x up to which a band's counters fit the LDS budget ...
+constexpr unsigned kRowCounterWords = 16000;  // ... of this many counters per workgroup (62.5 KB)
+constexpr unsigned kRowBandRows = 8;          // rows per band, unless nx or the number of bands asks otherwise
+constexpr unsigned kRowMaxBands = 8192;       // bands (counters in the LDS of k_rows_hist and k_rows_scatter)
+constexpr uint64_t kRowMaxTable = 1ull << 22; // entries of hist[band][tile]
+
+// exclusive prefix sums of a[0 .. n) in LDS, in place, by the whole workgroup (a[] complete and visible on entry: the
+// caller's barrier; visible again on return); returns the total.  s_wave: kRowThreads / 64 words.
+__device__ __forceinline__ unsigned rows_lds_scan(unsigned *a, unsigned n, unsigned *s_wave) {
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const unsigned per = (n + kRowThreads - 1) / kRowThreads;
+    const unsigned b = min(tid * per, n), e = min(b + per, n);
+    unsigned sum = 0;
+    for (unsigned i = b; i < e; ++i) sum += a[i];
+    const unsigned incl = wave_incl_scan(sum, lane);
+    if (lane == 63u) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - sum, all = 0;
+    for (unsigned w = 0; w < (unsigned) (kRowThreads / 64); ++w) {
+        if (w < wave) run += s_wave[w];
+        all += s_wave[w];
+    }
+    for (unsigned i = b; i < e; ++i) {
+        const unsigned v = a[i];
+        a[i] = run;
+        run += v;
+    }
+    __syncthreads();
+    return all;
+}
+
+__global__ void __launch_bounds__(kRowThreads) k_rows_hist(const float4 *__restrict__ pts, unsigned n, LinearKey key, unsigned rshift,
+                                                            unsigned bands, unsigned tiles, unsigned *__restrict__ hist) {
+    extern __shared__ unsigned s_mem[];  // [bands]
+    const unsigned tid = threadIdx.x, tile = blockIdx.x;
+    for (unsigned b = tid; b < bands; b += kRowThreads) s_mem[b] = 0u;
+    __syncthreads();
+    float4 p[8];
+#pragma unroll
+    for (unsigned r = 0; r < 8u; ++r) {  // eight loads in flight
+        const unsigned i = tile * (unsigned) kRowTile + r * kRowThreads + tid;
+        p[r] = i < n ? pts[i] : make_float4(NAN, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (unsigned r = 0; r < 8u; ++r)
+        if (p[r].x == p[r].x) {
+            unsigned row, cx;
+            key.row_x(p[r], &row, &cx);
+            atomicAdd(&s_mem[row >> rshift], 1u);
+        }
+    __syncthreads();
+    for (unsigned b = tid; b < bands; b += kRowThreads) hist[(size_t) b * tiles + tile] = s_mem[b];
+}
+
+__global__ void __launch_bounds__(kRowThreads) k_rows_scatter(const float4 *__restrict__ pts, unsigned n, LinearKey key, unsigned rshift,
+                                                               unsigned bands, unsigned tiles, const unsigned *__restrict__ hist,
+                                                               const unsigned *__restrict__ totals, unsigned *__restrict__ band_start,
+                                                               float4 *__restrict__ tmp) {
+    extern __shared__ unsigned s_mem[];  // [bands]: the cursor of each band's run for this tile
+    __shared__ unsigned s_wave[kRowThreads / 64];
+    const unsigned tid = threadIdx.x, tile = blockIdx.x;
+    float4 p[8];
+#pragma unroll
+    for (unsigned r = 0; r < 8u; ++r) {
+        const unsigned i = tile * (unsigned) kRowTile + r * kRowThreads + tid;
+        p[r] = i < n ? pts[i] : make_float4(NAN, 0.f, 0.f, 0.f);
+    }
+    for (unsigned b = tid; b < bands; b += kRowThreads) s_mem[b] = totals[b];
+    __syncthreads();
+    const unsigned all = rows_lds_scan(s_mem, bands, s_wave);
+    if (tile == 0) {
+        for (unsigned b = tid; b < bands; b += kRowThreads) band_start[b] = s_mem[b];
+        if (tid == 0) band_start[bands] = all;
+    }
+    for (unsigned b = tid; b < bands; b += kRowThreads) s_mem[b] += hist[(size_t) b * tiles + tile];
+    __syncthreads();
+#pragma unroll
+    for (unsigned r = 0; r < 8u; ++r)
+        if (p[r].x == p[r].x) {
+            unsigned row, cx;
+            key.row_x(p[r], &row, &cx);
+            tmp[atomicAdd(&s_mem[row >> rshift], 1u)] = p[r];
+        }
+}
+
+// A workgroup takes a band, i.e. ONE contiguous stretch of the band-ordered points, and all its threads walk that stretch
+// together -- whether it is eight rows of fifty points or one of them holds seventy thousand.  Pass 1 counts the points
+// per cell in LDS; a scan turns the counts into the cells' offsets in the stretch; the band's stretch of cell_start
+// leaves in coalesced runs (an empty band's words too); pass 2 reads the points again (from the cache) and draws each
+// one's slot from its cell's offset, now a cursor.  The last band's workgroup also writes cell_start[ncells] and the four
+// NaN entries behind the last point (see k_pad_tail).
+__global__ void __launch_bounds__(kRowThreads) k_rows_finish(const float4 *__restrict__ tmp, const unsigned *__restrict__ band_start,
+                                                              LinearKey key, unsigned nrows, unsigned rshift,
+                                                              unsigned *__restrict__ cell_start, float4 *__restrict__ out) {
+    extern __shared__ unsigned s_mem[];  // [rows of the band][nx]
+    __shared__ unsigned s_wave[kRowThreads / 64];
+    const unsigned nx = (unsigned) key.nx, tid = threadIdx.x;
+    const unsigned r0 = blockIdx.x << rshift;
+    const unsigned cells = min(1u << rshift, nrows - r0) * nx;
+    const unsigned s = band_start[blockIdx.x], e = band_start[blockIdx.x + 1];
+    for (unsigned k = tid; k < cells; k += kRowThreads) s_mem[k] = 0u;
+    __syncthreads();
+    for (unsigned j0 = s + tid; j0 < e; j0 += 4u * kRowThreads) {
+        float4 p[4];
+#pragma unroll
+        for (unsigned u = 0; u < 4u; ++u) {  // four loads in flight
+            const unsigned j = j0 + u * kRowThreads;
+            p[u] = j < e ? tmp[j] : make_float4(NAN, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (unsigned u = 0; u < 4u; ++u)
+            if (j0 + u * kRowThreads < e) {
+                unsigned row, cx;
+                key.row_x(p[u], &row, &cx);
+                atomicAdd(&s_mem[min((row - r0) * nx + cx, cells - 1u)], 1u);
+            }
+    }
+    __syncthreads();
+    if (e != s) rows_lds_scan(s_mem, cells, s_wave);  // (an empty band's counters are its offsets already)
+    unsigned *cs = cell_start + (size_t) r0 * nx;
+    for (unsigned k = tid; k < cells; k += kRowThreads) cs[k] = s + s_mem[k];
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+        cs[cells] = e;
+        const float nanv = __builtin_nanf("");
+#pragma unroll
+        for (int u = 0; u < 4; ++u) out[e + u] = make_float4(nanv, nanv, nanv, __uint_as_float(kNoIdx));
+    }
+    __syncthreads();
+    for (unsigned j0 = s + tid; j0 < e; j0 += 4u * kRowThreads) {
+        float4 p[4];
+#pragma unroll
+        for (unsigned u = 0; u < 4u; ++u) {
+            const unsigned j = j0 + u * kRowThreads;
+            p[u] = j < e ? tmp[j] : make_float4(NAN, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (unsigned u = 0; u < 4u; ++u)
+            if (j0 + u * kRowThreads < e) {
+                unsigned row, cx;
+                key.row_x(p[u], &row, &cx);
+                out[s + atomicAdd(&s_mem[min((row - r0) * nx + cx, cells - 1u)], 1u)] = p[u];
+            }
+    }
+}
+
+// WHERE the row-wise sort is taken, and with how many rows per band (2^*rshift): a pure function of the option
+// (grid_rows), the lattice and the number of points.
+//   structurally: a band's counters must fit the finish kernel's LDS budget (nx <= kRowNxCap), the bands' counters that
+//   of the other two kernels (kRowMaxBands), and the table of the tiles' counts stays small beside the points;
+//   where it pays (option 1): rows of at least 3 cells, enough bands to give every compute unit a workgroup of
+//   k_rows_finish, and enough points that the four launches' fixed cost is not the whole of it
+constexpr unsigned kRowMinRows = 2048, kRowMinPoints = 32768;
+static bool rows_apply(int option, int nx, int ny, int nz, size_t n, unsigned *rshift) {
+    if (option == 0 || n == 0 || (unsigned) nx > kRowNxCap) return false;
+    const uint64_t nrows = (uint64_t) ny * nz;
+    unsigned sh = 0;
+    while ((2u << sh) <= kRowBandRows && (2u << sh) * (unsigned) nx <= kRowCounterWords) ++sh;
+    while (((nrows - 1) >> sh) + 1 > kRowMaxBands && (2u << sh) * (unsigned) nx <= kRowCounterWords) ++sh;
+    const uint64_t bands = ((nrows - 1) >> sh) + 1, tiles = (n + kRowTile - 1) / kRowTile;
+    if (bands > kRowMaxBands || bands * tiles > kRowMaxTable) return false;
+    *rshift = sh;
+    if (option == 2) return true;
+    return nx >= 3 && nrows >= kRowMinRows && n >= kRowMinPoints;
+}
+static_assert(kRowCounterWords / kRowNxCap >= 1 && kRowCounterWords * sizeof(unsigned) + 64 <= 65536, "k_rows_finish's LDS");
+
+static int counting_sort_rows(wm_ctx *ctx, const float4 *pts, size_t n, const LinearKey &key, unsigned rshift,
+                              unsigned *cell_start /* ncells+1 */, float4 *out) {
+    const unsigned nrows = (unsigned) key.ny * (unsigned) key.nz;
+    const unsigned bands = ((nrows - 1) >> rshift) + 1, tiles = (unsigned) ((n + kRowTile - 1) / kRowTile);
+    WM_HIP(ctx, ctx->row_tmp.reserve(n * sizeof(float4)));
+    WM_HIP(ctx, ctx->row_hist.reserve(((size_t) bands * tiles + 2 * (size_t) bands + 1) * sizeof(unsigned)));
+    unsigned *hist = ctx->row_hist.as<unsigned>(), *totals = hist + (size_t) bands * tiles, *band_start = totals + bands;
+    float4 *tmp = ctx->row_tmp.as<float4>();
+    const size_t band_lds = (size_t) bands * sizeof(unsigned);
+    hipLaunchKernelGGL(k_rows_hist, dim3(tiles), dim3(kRowThreads), band_lds, ctx->stream, pts, (unsigned) n, key, rshift, bands, tiles, hist);
+    WM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_rs_scan, dim3(bands), dim3(kRsThreads), 0, ctx->stream, hist, tiles, totals);
+    WM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_rows_scatter, dim3(tiles), dim3(kRowThreads), band_lds, ctx->stream, pts, (unsigned) n, key, rshift, bands, tiles,
+                       (const unsigned *) hist, (const unsigned *) totals, band_start, tmp);
+    WM_HIP(ctx, hipGetLastError());
+    const size_t cell_lds = ((size_t) key.nx << rshift) * sizeof(unsigned);
+    hipLaunchKernelGGL(k_rows_finish, dim3(bands), dim3(kRowThreads), cell_lds, ctx->stream, (const float4 *) tmp,
+                       (const unsigned *) band_start, key, nrows, rshift, cell_start, out);
+    WM_HIP(ctx, hipGetLastError());
+    return WM_OK;
+}
+
+// occupied-cell count (for choosing the level-0 cell size): one partial per workgroup,
+// summed by the host
 // occupied-cell count (for choosing the level-0 cell size): one partial per workgroup,
 // summed by the host
 constexpr int kOccBlocks = 1024;
@@ -396,7 +616,10 @@ int build_grid_level(wm_ctx *ctx, const float4 *pts, size_t n, const Bbox &bb, f
     WM_HIP(ctx, lvl->pts.reserve((n + 4) * sizeof(float4)));
     WM_HIP(ctx, lvl->cell_start.reserve((ncells + 1) * sizeof(unsigned)));
     LinearKey key{bb.lo[0], bb.lo[1], bb.lo[2], 1.0f / h, nx, ny, nz};
-    if (n > 0) {
+    unsigned rshift = 0;
+    if (rows_apply(ctx->tune_grid_rows, nx, ny, nz, n, &rshift)) {
+        WM_TRY(counting_sort_rows(ctx, pts, n, key, rshift, lvl->cell_start.as<unsigned>(), lvl->pts.as<float4>()));
+    } else if (n > 0) {
         WM_TRY(counting_sort(ctx, pts, n, key, ncells, lvl->cell_start.as<unsigned>(),
                              lvl->pts.as<float4>()));
     } else {
@@ -569,9 +792,11 @@ __global__ void __launch_bounds__(kBlock)
     }
     if (j >= fs[fncells]) return;
     const float4 p = fpts[j];
-    int x = min(max((int) floorf((p.x - key0.ox) * key0.inv_h), 0), key0.nx - 1) >> shift;
-    int y = min(max((int) floorf((p.y - key0.oy) * key0.inv_h), 0), key0.ny - 1) >> shift;
-    int z = min(max((int) floorf((p.z - key0.oz) * key0.inv_h), 0), key0.nz - 1) >> shift;
+    int x, y, z;
+    key0.cell(p, &x, &y, &z);
+    x >>= shift;
+    y >>= shift;
+    z >>= shift;
     const int X = x >> 1, Y = y >> 1, Z = z >> 1, r = (y & 1) + 2 * (z & 1);
     unsigned dst = cs[((size_t) Z * cny + Y) * cnx + X];
     for (int q = 0; q < r; ++q) {

@@ -318,6 +318,7 @@ struct wm_ctx {
     int tune_sac_round = 256;    // stream entries a round of the RANSAC loop evaluates at the most (1 ... 1024)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
+    int tune_grid_rows = 1;      // a grid level's counting sort by (y, z) rows: 1 where it pays (rows_apply, wm_grid.hip), 0 never, 2 wherever possible
     int tune_ndt_dense = 2;      // 0: hash grid; 1: dense cell -> slot table; 2: + the float4 cell lattice
     int tune_ndt_vox_split = -1; // developer: points per voxel up to which a LANE forms a voxel's sums (-1: ndt_build's choice)
     int tune_ndt_keys64 = 0;     // developer: 64-bit voxel sort keys whatever the lattice's size
@@ -340,6 +341,9 @@ struct wm_ctx {
 
     // scratch
     wm::DevBuf staging, staging2, cell_of, counts, block_sums, bbox_buf;
+    // the row-wise counting sort (wm_grid.hip): the tiles' counts per band of rows (+ the bands' totals and first
+    // slots), the points ordered by band
+    wm::DevBuf row_hist, row_tmp;
     wm::DevBuf match_pt, match_pt_bak;  // float4 per (sorted) source point: its match's xyz
     wm::PairStage icp_stage, gicp_stage, ndt_stage;  // staging of the batched small registrations (wm_small.hip, wm_gicp_small.hip, wm_ndt_small.hip)
     void *batch_voxel = nullptr;            // wm_batch.hip: buffers of the batched voxel filter
