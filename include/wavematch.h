@@ -1237,6 +1237,97 @@ int wm_feature_match(wm_ctx *ctx, const void *a, size_t na, size_t a_stride_byte
                      size_t b_stride_bytes, int mem, int reciprocal, int32_t *idx_out, float *d2_out /* NULL ok */,
                      int out_mem, wm_feature_match_stats *stats /* NULL ok */);
 
+/* ------------------------------------------------------------- pose from correspondences */
+/* pcl::registration::CorrespondenceRejectorSampleConsensus on the device: RANSAC over a list of correspondences with
+ * SampleConsensusModelRegistration (a rigid transform from three pairs); out come the best transformation and the
+ * correspondences it keeps.  The third stage behind wm_fpfh_estimate and wm_feature_match: a pose without a guess.
+ * [PCL-upstream: restated from PCL 1.8 registration/impl/correspondence_rejection_sample_consensus.hpp,
+ * sample_consensus/sac_model_registration.h and its impl, ransac.hpp; no PCL on the build machine]
+ * (tests/corr_ransac_reference.py is the checker).  Float arithmetic is float32, double is float64, every operation
+ * rounded and nothing fused; divisions and square roots are the IEEE ones.
+ *   input        src (n_src records) and tgt (n_tgt records), x y z first, one stride, in `mem`.  m entries: entry e
+ *                pairs source point query_idx[e] (query_idx == NULL: e, and then m <= n_src) with target point
+ *                match_idx[e]; both arrays int32 in `mem`.  With query_idx == NULL this is wm_feature_match's idx_out as
+ *                it is (-1: no match) and wm_get_correspondences' form.
+ *   pairs        an entry is VALID iff both indices are in range and both points are finite.  The valid entries,
+ *                ascending by e, are the pairs 0 ... mv - 1.  An invalid entry is labelled WM_CORR_NONE, never counts
+ *                and is never sampled.  DEVIATION: PCL samples over all its indices -- a reciprocal match keeps a
+ *                tenth of the rows, and a stream over all entries would skip 999 of 1000 triples.
+ *   stream       entry j is the plane segmentation's (i0, i1, i2) = sample(seed, j, mv), bit for bit: indices of pairs.
+ *   sample test  [isSampleGood]  the three squared distances between the sample's SOURCE points, (dx dx + dy dy) + dz dz
+ *                in float for (p0, p1), (p0, p2), (p1, p2), must each be > min_d2.  min_sample_distance >= 0: min_d2 =
+ *                the float nearest (double) d * d.  < 0 (the default, -1): [computeSampleDistanceThreshold]
+ *                ((sqrt l0 + sqrt l1 + sqrt l2) / 3)^2 with l the eigenvalues of the covariance of the pairs' source
+ *                points normalised by mv, clamped at 0.  DEVIATIONS: PCL's float sums are the nine sums in double
+ *                relative to pair 0's source point, added exactly (integer limbs, as the plane refit's); the eigenvalues
+ *                are the singular values of the one-sided Jacobi SVD on the host; the result is rounded to float, to
+ *                nearest; a sum the limbs cannot hold or a non-finite one gives min_d2 = 0.  ADDED: s = |(p1 - p0) x
+ *                (p2 - p0)|^2 in float as the plane rule forms it; the entry is SKIPPED iff a distance fails or s is
+ *                not finite or not > 0.
+ *   hypothesis   [computeModelCoefficients -> estimateRigidTransformationSVD; DEVIATION: its float centroids and
+ *                JacobiSVD<Matrix3f> are replaced]  the 17 statistics of wm_umeyama_from_stats in double from the three
+ *                pairs in sample order: n = 3, the sums (x0 + x1) + x2, the cross sums (q0a p0b + q1a p1b) + q2a p2b;
+ *                then that Umeyama step with no warm start and the IEEE-only one-sided Jacobi SVD.  Its twelve entries
+ *                (rows 0 ... 2 of [R | t]) are rounded to float, to nearest; a non-finite entry makes the stream
+ *                entry skipped.  wm_corr_hypothesis is this rule on the host.
+ *   count        [countWithinDistance]  x' = ((r00 x + r01 y) + r02 z) + tx, y' and z' alike; dx = x' - qx; d2 = (dx dx
+ *                + dy dy) + dz dz; a pair is an inlier iff d2 < thr2, thr2 = the smallest float not below (double)
+ *                inlier_threshold^2.  A source point matched by several entries counts once per entry (PCL's map keeps
+ *                one; with wm_feature_match's output the case does not arise).
+ *   loop         the plane segmentation's, with n = mv; an entry is valid or skipped.
+ *   no model     mv < 3 (no device work beyond finding mv; none at all with m < 3, or in host memory) or every entry
+ *                skipped: WM_NOT_CONVERGED, T_out untouched, *n_out = 0, labels_out not written.
+ *   refit        iff refine_model (default 0, PCL's refine_ = false) and the model has >= 3 inliers: the 17 statistics
+ *                over the model's inliers in double RELATIVE to the winning sample's first pair (p0, q0), added exactly
+ *                (integer limbs); the same Umeyama step on the host; t = q0 + t' - R p0.  T_out is the double result
+ *                and the inliers are selected once more with its float rounding.  A sum the limbs cannot hold, or a
+ *                non-finite result, keeps the model.  DEVIATION: PCL's refinement loop (re-estimate, shrink the threshold
+ *                by the residuals' variance, up to a number of rounds) is not built.
+ *   output       T_out: row-major 4 x 4 double on the host; without the refit the winning float entries widened.
+ *                inliers_out: the kept entries' positions e, ascending.  labels_out: m bytes.  Every output byte is a
+ *                function of the inputs and the parameters; how the stream is cut into rounds (option "corr_round",
+ *                default 256, 1 ... 1024) changes nothing but `rounds`. */
+typedef struct {
+    double inlier_threshold;     /* finite and > 0; PCL's default 0.05 */
+    int max_iterations;          /* >= 1; PCL's default 1000 */
+    double probability;          /* in (0, 1); 0.99 */
+    int refine_model;            /* default 0 */
+    double min_sample_distance;  /* finite; < 0 (default -1): from the pairs' source points */
+    uint64_t seed;               /* default 0 */
+} wm_corr_ransac_params;
+void wm_corr_ransac_default_params(wm_corr_ransac_params *p);
+
+enum { WM_CORR_NONE = 0 /* not a valid entry */, WM_CORR_INLIER = 1, WM_CORR_OUTLIER = 2 };
+typedef struct {
+    size_t n_valid /* mv */, n_inliers_model /* the winning hypothesis' count */, n_inliers /* returned */;
+    int iterations, skipped, rounds /* device rounds of the stream */, refined /* the refit replaced the model */;
+    long long hypotheses /* stream entries consumed */, best_hypothesis /* its stream index, -1: none */;
+    float min_d2;     /* the sample test's bound as it was applied */
+    float model[12];  /* the winning hypothesis before the refit */
+    float kernel_ms;  /* the front to the last output */
+} wm_corr_ransac_stats;
+
+/* T_out (host, 16 doubles).  inliers_out (cap entries) and labels_out (m bytes, WM_CORR_*) live in `out_mem`.  More
+ * inliers than `cap`: WM_ERR_ARG with the first `cap` written and *n_out the true count.  Argument errors, found
+ * before a device is touched: a null ctx / params / T_out / n_out; a bad stride (< 12 or no multiple of 4), mem or
+ * out_mem; n_src or n_tgt above 0x7FFFFFF0; m above WM_FEATURE_MAX_ROWS; query_idx == NULL with m > n_src; a null
+ * cloud with records; a null match_idx with m > 0; a null inliers_out with cap > 0; and the parameter ranges above.
+ * The workspace is the context's own (freed by wm_ctx_destroy); the registration state and every other workspace stay
+ * untouched. */
+int wm_corr_ransac(wm_ctx *ctx, const void *src, size_t n_src, const void *tgt, size_t n_tgt, size_t stride_bytes,
+                   const int32_t *query_idx /* NULL ok */, const int32_t *match_idx, size_t m, int mem,
+                   const wm_corr_ransac_params *params, double T_out[16], int32_t *inliers_out, size_t cap, int out_mem,
+                   size_t *n_out, uint8_t *labels_out /* NULL ok */, wm_corr_ransac_stats *stats /* NULL ok */);
+
+/* The hypothesis rule on the host (no device): p and q are the sample's three source and target points, x y z each, in
+ * sample order.  Returns 1 with T_out = the twelve floats, or 0 (skipped) with T_out zero; negative: a null argument. */
+int wm_corr_hypothesis(const float p[9], const float q[9], float min_d2, float T_out[12]);
+
+/* For tests and developers: entries j0 ... j0 + count - 1 (count <= 1024) of the hypothesis stream of the LAST
+ * wm_corr_ransac call on this context (its pairs, seed and min_d2), evaluated by the device: twelve floats and a flag
+ * (1 valid, 0 skipped) per entry, host memory.  WM_ERR_STATE without such a call or with fewer than 3 pairs. */
+int wm_debug_corr_hypotheses(wm_ctx *ctx, uint64_t j0, int count, float *T_out, uint32_t *flags_out);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -225,6 +225,22 @@ WM_FEATURE_DIM = 33
 WM_FEATURE_MAX_ROWS = 1 << 20  # rows per side of a feature_match
 
 
+class CorrRansacParams(C.Structure):
+    _fields_ = [("inlier_threshold", C.c_double), ("max_iterations", C.c_int), ("probability", C.c_double),
+                ("refine_model", C.c_int), ("min_sample_distance", C.c_double), ("seed", C.c_uint64)]
+
+
+class CorrRansacStats(C.Structure):
+    _fields_ = [("n_valid", C.c_size_t), ("n_inliers_model", C.c_size_t), ("n_inliers", C.c_size_t),
+                ("iterations", C.c_int), ("skipped", C.c_int), ("rounds", C.c_int), ("refined", C.c_int),
+                ("hypotheses", C.c_longlong), ("best_hypothesis", C.c_longlong), ("min_d2", C.c_float),
+                ("model", C.c_float * 12), ("kernel_ms", C.c_float)]
+
+
+WM_CORR_NONE, WM_CORR_INLIER, WM_CORR_OUTLIER = 0, 1, 2
+assert C.sizeof(CorrRansacParams) == 48 and C.sizeof(CorrRansacStats) == 112
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -410,6 +426,13 @@ def lib():
                                        C.c_int, C.POINTER(FpfhStats)]
         L.wm_feature_match.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(FeatureMatchStats)]
+        L.wm_corr_ransac_default_params.argtypes = [C.POINTER(CorrRansacParams)]
+        L.wm_corr_ransac_default_params.restype = None
+        L.wm_corr_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CorrRansacParams), _dp, C.c_void_p,
+                                     C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(CorrRansacStats)]
+        L.wm_corr_hypothesis.argtypes = [_fp, _fp, C.c_float, _fp]
+        L.wm_debug_corr_hypotheses.argtypes = [C.c_void_p, C.c_uint64, C.c_int, _fp, C.POINTER(C.c_uint32)]
         _LIB = L
     return _LIB
 
@@ -564,6 +587,46 @@ def sac_params(params=None, **kw):
             raise AttributeError(k)
         setattr(p, k, (C.c_double * 3)(*[float(x) for x in v]) if k == "axis" else v)
     return p
+
+
+def corr_ransac_params(params=None, **kw):
+    """wm_corr_ransac_params from PCL's defaults (wm_corr_ransac_default_params), a dict of field values and keywords."""
+    p = CorrRansacParams()
+    lib().wm_corr_ransac_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def corr_hypothesis(p, q, min_d2=0.0):
+    """wm_corr_hypothesis, the hypothesis rule of wm_corr_ransac on the host (no device): p, q float32 (3, 3), the
+    sample's source and target points in sample order -> (flag, T float32 (3, 4)); flag 0: skipped, T zero."""
+    p = np.ascontiguousarray(p, dtype=np.float32).reshape(9)
+    q = np.ascontiguousarray(q, dtype=np.float32).reshape(9)
+    T = np.zeros(12, np.float32)
+    flag = lib().wm_corr_hypothesis(p.ctypes.data_as(_fp), q.ctypes.data_as(_fp), C.c_float(float(np.float32(min_d2))),
+                                    T.ctypes.data_as(_fp))
+    if flag < 0:
+        raise WmError("wm_corr_hypothesis: %s" % lib().wm_strerror(flag).decode())
+    return flag, T.reshape(3, 4)
+
+
+def _index_arg(a, mem):
+    """-> (pointer, n, keepalive) of an int32 index array living in `mem`."""
+    if mem == WM_MEM_HOST:
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        assert a.ndim == 1
+        return a.ctypes.data, a.shape[0], a
+    import torch
+    if isinstance(a, np.ndarray):
+        raise TypeError("the clouds are on the device: the indices must be a HIP torch tensor too")
+    assert isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.dim() == 1 and a.is_cuda
+    a = a.contiguous()
+    return a.data_ptr(), a.shape[0], a
 
 
 def _cloud_arg(a):
@@ -1415,6 +1478,67 @@ class Context:
         self._check(lib().wm_feature_match(self._h, C.c_void_p(pa), na, sa, C.c_void_p(pb), nb, sb, mem, int(bool(reciprocal)),
                                            C.c_void_p(pi), C.c_void_p(pd), mem, C.byref(st)), "wm_feature_match")
         return dict(idx=idx[:na], d2=d2[:na], n_matched=st.n_matched, kernel_ms=st.kernel_ms)
+
+    def corr_ransac(self, src, tgt, match_idx, query_idx=None, params=None, labels=True, out_mem=None, cap=None, **kw):
+        """pcl::registration::CorrespondenceRejectorSampleConsensus on the device (wm_corr_ransac) -> dict: rc (WM_OK,
+        WM_NOT_CONVERGED without a model, WM_ERR_ARG with more inliers than `cap`), T (4, 4) float64 (None without a
+        model), inliers (the kept entries' positions, ascending, int32), labels (m,) uint8 (WM_CORR_NONE / INLIER /
+        OUTLIER; None with labels=False or without a model), n_out and the fields of wm_corr_ransac_stats (model as a
+        (3, 4) float32 array).  src, tgt: float32 (n, 3|4) numpy arrays or HIP torch tensors of one kind.  match_idx
+        (and query_idx): int32 (m,) where the clouds live -- feature_match(...)["idx"] as it is.  out_mem: where
+        inliers and labels are written; by default where the clouds live.  `params`: a CorrRansacParams, a dict of its
+        fields, or None (PCL's defaults); keywords override fields.  cap: room for the inliers (default m)."""
+        ps, n_src, stride, mem, keep_s = _cloud_arg(src)
+        pt, n_tgt, stride_t, mem_t, keep_t = _cloud_arg(tgt)
+        assert mem == mem_t and stride == stride_t
+        pm, m, keep_m = _index_arg(match_idx, mem)
+        pq, keep_q = None, None
+        if query_idx is not None:
+            pq, mq, keep_q = _index_arg(query_idx, mem)
+            assert mq == m
+        if isinstance(params, CorrRansacParams):
+            params = {k: getattr(params, k) for k, _ in CorrRansacParams._fields_}
+        p = corr_ransac_params(params, **kw)
+        out_mem = mem if out_mem is None else out_mem
+        cap = m if cap is None else int(cap)
+        n_out = C.c_size_t(0)
+        st = CorrRansacStats()
+        T = np.zeros((4, 4), np.float64)
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = src.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            lab = torch.zeros(max(m, 1), dtype=torch.uint8, device=dev) if labels else None
+            idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            lab = np.zeros(max(m, 1), np.uint8) if labels else None
+            idx = np.empty(max(cap, 1), np.int32)
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = lib().wm_corr_ransac(self._h, C.c_void_p(ps), n_src, C.c_void_p(pt), n_tgt, stride, C.c_void_p(pq),
+                                  C.c_void_p(pm), m, mem, C.byref(p), T.ctypes.data_as(_dp), addr(idx), cap, out_mem,
+                                  C.byref(n_out), addr(lab), C.byref(st))
+        if rc < 0 and not (rc == WM_ERR_ARG and n_out.value > cap):  # (more inliers than cap: the caller's to handle)
+            self._check(rc, "wm_corr_ransac")
+        found = rc == WM_OK or (rc == WM_ERR_ARG and n_out.value > cap)
+        out = dict(rc=rc, T=T if found else None, inliers=idx[:min(n_out.value, cap)],
+                   labels=lab[:m] if labels and found else None, n_out=n_out.value)
+        out.update({f: getattr(st, f) for f, _ in CorrRansacStats._fields_})
+        out["model"] = np.array(st.model[:], np.float32).reshape(3, 4)
+        return out
+
+    def debug_corr_hypotheses(self, j0, count):
+        """wm_debug_corr_hypotheses: entries j0 ... j0 + count - 1 of the last corr_ransac call's hypothesis stream as
+        the device evaluates them -> (T float32 (count, 3, 4), flags uint32 (count,))."""
+        T = np.zeros((count, 12), np.float32)
+        fl = np.zeros(count, np.uint32)
+        self._check(lib().wm_debug_corr_hypotheses(self._h, int(j0), int(count), T.ctypes.data_as(_fp),
+                                                   fl.ctypes.data_as(C.POINTER(C.c_uint32))), "wm_debug_corr_hypotheses")
+        return T.reshape(count, 3, 4), fl
 
     # ---- NDT
     def ndt_align(self, params=None, **kw):

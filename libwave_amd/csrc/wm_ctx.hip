@@ -237,6 +237,8 @@ const Option kOptions[] = {
     {"cluster_cell_div", "WM_TUNE_CLUSTER_CELL_DIV", nullptr, &wm_ctx::tune_cluster_cell_div, 0.5, 8, 0},
     // plane segmentation (wm_sac.hip)
     {"sac_round", "WM_TUNE_SAC_ROUND", &wm_ctx::tune_sac_round, nullptr, 1, 1024, 0},
+    // pose from correspondences (wm_corr_ransac.hip)
+    {"corr_round", "WM_TUNE_CORR_ROUND", &wm_ctx::tune_corr_round, nullptr, 1, 1024, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
     // the grids' counting sort (wm_grid.hip)
@@ -334,6 +336,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     sac_release(ctx);
     boxes_release(ctx);
     fpfh_release(ctx);
+    corr_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

@@ -316,6 +316,8 @@ struct wm_ctx {
     float tune_cluster_cell_div = 2.f;  // the clustering's grid cell is at least tolerance / this (0.5 ... 8)
     // plane segmentation (wm_sac.hip)
     int tune_sac_round = 256;    // stream entries a round of the RANSAC loop evaluates at the most (1 ... 1024)
+    // pose from correspondences (wm_corr_ransac.hip)
+    int tune_corr_round = 256;   // the same for the RANSAC over correspondences (1 ... 1024)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_grid_rows = 1;      // a grid level's counting sort by (y, z) rows: 1 where it pays (rows_apply, wm_grid.hip), 0 never, 2 wherever possible
@@ -353,6 +355,7 @@ struct wm_ctx {
     void *sac = nullptr;                    // wm_sac.hip: the plane segmentation's workspace (its own as well)
     void *boxes = nullptr;                  // wm_describe.hip: the cluster boxes' workspace (its own as well)
     void *fpfh = nullptr;                   // wm_fpfh.hip, wm_feature_match.hip: the descriptors' workspace (its own as well)
+    void *corr = nullptr;                   // wm_corr_ransac.hip: the workspace of the RANSAC over correspondences (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -675,6 +678,9 @@ void boxes_release(wm_ctx *ctx);
 
 // ---- wm_fpfh.hip (the workspace both descriptor files share; wm_feature_match.hip's part is released with it)
 void fpfh_release(wm_ctx *ctx);
+
+// ---- wm_corr_ransac.hip
+void corr_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0

@@ -354,6 +354,9 @@ WM_HD void rodrigues(const double *w, double *R) {
 // Eigen/src/Geometry/Umeyama.h], driven by wave_matching/src/icp.cpp:126.
 // Vwarm (may be null): in, an orthogonal starting basis for the SVD (see svd3) unless Vwarm[9]
 // is 0; out, this call's V and Vwarm[9] = 1.
+// FAST: svd3's (the registrations' solve: true).  !FAST: IEEE divisions and square roots only, so that a lane and the
+// host give the same bits (wm_corr_rule.hpp).
+template <bool FAST = true>
 WM_HD void umeyama_from_stats(const double *st, double *T, double *Vwarm = nullptr) {
     const double n = st[kSvdN];
     double pm[3], qm[3], sigma[9], U[9], S[3], V[9], R[9];
@@ -367,7 +370,7 @@ WM_HD void umeyama_from_stats(const double *st, double *T, double *Vwarm = nullp
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) sigma[i * 3 + j] = st[kSvdSqp + i * 3 + j] * one_over_n - qm[i] * pm[j];
-    svd3(sigma, U, S, V, (Vwarm && Vwarm[9] != 0.0) ? Vwarm : nullptr);
+    svd3<FAST>(sigma, U, S, V, (Vwarm && Vwarm[9] != 0.0) ? Vwarm : nullptr);
     if (Vwarm) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) Vwarm[i] = V[i];
