@@ -1328,6 +1328,82 @@ int wm_corr_hypothesis(const float p[9], const float q[9], float min_d2, float T
  * (1 valid, 0 skipped) per entry, host memory.  WM_ERR_STATE without such a call or with fewer than 3 pairs. */
 int wm_debug_corr_hypotheses(wm_ctx *ctx, uint64_t j0, int count, float *T_out, uint32_t *flags_out);
 
+/* ------------------------------------------------------------- keypoints */
+/* pcl::ISSKeypoint3D on the device: the few points of a cloud worth matching, in front of wm_feature_match (describe
+ * all points, keep the keypoints' rows with wm_gather_records, match those).
+ * [PCL-upstream: restated from PCL 1.8 keypoints/impl/iss_3d.hpp, getScatterMatrix and detectKeypoints; no PCL on the
+ * build machine] (tests/iss_reference.py is the checker).  Float is float32, double is float64, every operation
+ * rounded and nothing fused.
+ *   neighbours   r2s = (float) (salient_radius * salient_radius), r2n = (float) (non_max_radius * non_max_radius), the
+ *                products in double.  A neighbour of finite point i is a finite point j with d2(i, j) < r2 (strict, as
+ *                FLANN's radius set), i itself included; d2 = (dx dx + dy dy) + dz dz in float, the form every other
+ *                call uses.  A non-finite point is nobody's neighbour and gets WM_ISS_NONE.
+ *   scatter      for each neighbour j within r2s: d = p_j - p_i, three float subtractions, widened (as PCL); the six
+ *                products dx dx, dx dy, dx dz, dy dy, dy dz, dz dz in double (exact: 24 + 24 bits).  Each enters its
+ *                sum as the integer rint(product * scale), ties to even, scale = 2^(36 - x) with r2s = m 2^x, m in
+ *                [0.5, 1) (frexp); the integers are added exactly in int64.  DEVIATION: PCL adds the doubles in its
+ *                kd-tree's order; here the sum must not depend on the order of the points inside a grid cell, and a
+ *                set of integers has one sum.  The quantum is 2^-36 of r2s; a term is below about 2^36 and n is at
+ *                most WM_ISS_MAX_POINTS (2^26), so an int64 cannot overflow.  n_s: the number of neighbours, i included.
+ *   saliency     n_s < min_neighbors: third = 0.  Otherwise the six sums, converted to double (round to nearest), form
+ *                the symmetric matrix; its eigenvalues by cyclic Jacobi sweeps (the library's jacobi3), sorted l1 >= l2
+ *                >= l3.  Point i is SALIENT iff the three are finite, l3 > 0, l2 / l1 < gamma_21 and l3 / l2 < gamma_32
+ *                (divisions in double; a NaN fails).  A salient point has third = ldexp(l3, x - 36), every other point
+ *                third = 0.  wm_iss_third is this step on the host.  DEVIATIONS: the Jacobi sweeps stand in for Eigen's
+ *                SelfAdjointEigenSolver; PCL leaves a stale thread-local value behind when it skips a point with l3 < 0
+ *                or a non-finite value -- here such a point is simply not salient; there is no border estimation
+ *                (border_radius, normal_radius and angle_threshold do not exist).
+ *   suppression  point i is a KEYPOINT iff third_i > 0, the number of its neighbours within r2n (i included) is >=
+ *                min_neighbors, and no such neighbour j has third_j > third_i (strict).  Equal values survive together,
+ *                as PCL's `<` test leaves them (exact duplicates are the case that arises).
+ *   output       the keypoints' caller indices, ascending (PCL's order).  Every output byte is a function of the inputs
+ *                and the parameters: not of the grid's cell (option "iss_cell_div", default 2, 0.5 ... 8: the cell is
+ *                at least max(salient_radius, non_max_radius) / iss_cell_div), nor of the order of rows that are not
+ *                compared. */
+typedef struct {
+    double salient_radius;   /* finite, (float) r^2 a normal float > 0; no usable default: 0 */
+    double non_max_radius;   /* the same */
+    double gamma_21;         /* finite, >= 0; 0.975 */
+    double gamma_32;         /* finite, >= 0; 0.975 */
+    int min_neighbors;       /* >= 0; 5 */
+} wm_iss_params;
+void wm_iss_default_params(wm_iss_params *p);
+
+typedef struct {
+    size_t n_finite, n_salient, n_keypoints;
+    float kernel_ms;  /* the front to the keypoint list */
+} wm_iss_stats;
+
+enum { WM_ISS_NONE = 0 /* non-finite */, WM_ISS_PLAIN = 1, WM_ISS_SALIENT = 2 /* third > 0, suppressed */, WM_ISS_KEYPOINT = 3 };
+#define WM_ISS_MAX_POINTS 0x4000000ull /* n at most: 2^26 */
+
+/* The cloud (x y z first in each record) lives in `mem`; indices_out (cap entries), labels_out (n bytes, WM_ISS_*),
+ * third_out (n doubles; 0 for a point that is not salient) and counts_out (n: n_s, -1 for a non-finite point) live in
+ * `out_mem`.  More keypoints than `cap`: WM_ERR_ARG with the first `cap` written and *n_out the true count.  A cloud
+ * without a finite point, or without a keypoint, is WM_OK with *n_out = 0.  Argument errors, found before a device is
+ * touched: a null ctx / params / n_out; a null cloud with n > 0; a bad stride (< 12 or no multiple of 4), mem or
+ * out_mem; n above WM_ISS_MAX_POINTS; a null indices_out with cap > 0; and the parameter ranges above.  n == 0 is
+ * WM_OK with no device touched.  The workspace is the context's own (freed by wm_ctx_destroy); the registration state
+ * and every other workspace stay untouched.  The counters come back in one copy behind the last kernel, and the host
+ * waits there (and once in the front, for the cloud's box, as wm_outlier_filter). */
+int wm_iss_keypoints(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, const wm_iss_params *p,
+                     int32_t *indices_out, size_t cap, int out_mem, size_t *n_out, uint8_t *labels_out /* NULL ok */,
+                     double *third_out /* NULL ok */, int32_t *counts_out /* NULL ok */, wm_iss_stats *stats /* NULL ok */);
+
+/* The saliency step on the host (no device): the six integer sums (xx xy xz yy yz zz), n_s and x (r2s = m 2^x, -125
+ * <= x <= 128) -> *third_out.  Of `p` only gamma_21, gamma_32 and min_neighbors are read.  WM_ERR_ARG: a null
+ * argument, x or one of those three out of range. */
+int wm_iss_third(const int64_t sums[6], int n_s, int x, const wm_iss_params *p, double *third_out);
+
+/* Record j of dst = record idx[j] of src (n records of stride_bytes, a multiple of 4 up to WM_GATHER_MAX_STRIDE), j <
+ * m; src, idx and dst all live in `mem` and do not overlap.  It selects the keypoints' rows of wm_fpfh_estimate's
+ * output for wm_feature_match.  An index outside [0, n) gives WM_ERR_ARG: nothing is read out of range, that record of
+ * dst is not written (host memory: nothing is written at all).  n and m at most 0x7FFFFFF0; m == 0 is WM_OK with no
+ * device touched.  Device memory: one kernel, one counter back. */
+#define WM_GATHER_MAX_STRIDE 65536u
+int wm_gather_records(wm_ctx *ctx, const void *src, size_t n, size_t stride_bytes, const int32_t *idx, size_t m,
+                      void *dst, int mem);
+
 /* All ranks in ONE process: one context and one worker thread per device, RCCL communicators from
  * ncclCommInitAll (emulate != 0: `n_devices` ranks on devices[0] with the host stand-in exchange).
  * wm_multi_icp_align runs one sharded registration of two HOST clouds (uploaded once, broadcast over

@@ -241,6 +241,21 @@ WM_CORR_NONE, WM_CORR_INLIER, WM_CORR_OUTLIER = 0, 1, 2
 assert C.sizeof(CorrRansacParams) == 48 and C.sizeof(CorrRansacStats) == 112
 
 
+class IssParams(C.Structure):
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double),
+                ("gamma_32", C.c_double), ("min_neighbors", C.c_int)]
+
+
+class IssStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("n_salient", C.c_size_t), ("n_keypoints", C.c_size_t), ("kernel_ms", C.c_float)]
+
+
+WM_ISS_NONE, WM_ISS_PLAIN, WM_ISS_SALIENT, WM_ISS_KEYPOINT = 0, 1, 2, 3
+WM_ISS_MAX_POINTS = 1 << 26   # points of an iss_keypoints call
+WM_GATHER_MAX_STRIDE = 65536  # bytes of a gather_records record
+assert C.sizeof(IssParams) == 40 and C.sizeof(IssStats) == 32
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -433,6 +448,14 @@ def lib():
                                      C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(CorrRansacStats)]
         L.wm_corr_hypothesis.argtypes = [_fp, _fp, C.c_float, _fp]
         L.wm_debug_corr_hypotheses.argtypes = [C.c_void_p, C.c_uint64, C.c_int, _fp, C.POINTER(C.c_uint32)]
+        L.wm_iss_default_params.argtypes = [C.POINTER(IssParams)]
+        L.wm_iss_default_params.restype = None
+        L.wm_iss_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(IssParams),
+                                       C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(IssStats)]
+        L.wm_iss_third.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(IssParams), _dp]
+        L.wm_gather_records.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_int]
         _LIB = L
     return _LIB
 
@@ -611,6 +634,33 @@ def corr_hypothesis(p, q, min_d2=0.0):
     if flag < 0:
         raise WmError("wm_corr_hypothesis: %s" % lib().wm_strerror(flag).decode())
     return flag, T.reshape(3, 4)
+
+
+def iss_params(params=None, **kw):
+    """wm_iss_params from wm_iss_default_params (gamma 0.975, min_neighbors 5; the two radii must be set), a dict of
+    field values and keywords."""
+    p = IssParams()
+    lib().wm_iss_default_params(C.byref(p))
+    for k, v in dict(params or {}, **kw).items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def iss_third(sums, n_s, x, params=None, **kw):
+    """wm_iss_third, the saliency step of wm_iss_keypoints on the host (no device): the six integer scatter sums (xx xy
+    xz yy yz zz), the neighbour count and x (r2s = m 2^x) -> third (float).  Of the parameters only gamma_21, gamma_32
+    and min_neighbors are read."""
+    if isinstance(params, IssParams):
+        params = {k: getattr(params, k) for k, _ in IssParams._fields_}
+    p = iss_params(params, **kw)
+    s = (C.c_int64 * 6)(*[int(v) for v in sums])
+    out = C.c_double(0.0)
+    rc = lib().wm_iss_third(s, int(n_s), int(x), C.byref(p), C.byref(out))
+    if rc != WM_OK:
+        raise WmError("wm_iss_third: %s" % lib().wm_strerror(rc).decode())
+    return out.value
 
 
 def _index_arg(a, mem):
@@ -1539,6 +1589,74 @@ class Context:
         self._check(lib().wm_debug_corr_hypotheses(self._h, int(j0), int(count), T.ctypes.data_as(_fp),
                                                    fl.ctypes.data_as(C.POINTER(C.c_uint32))), "wm_debug_corr_hypotheses")
         return T.reshape(count, 3, 4), fl
+
+    def iss_keypoints(self, cloud, params=None, labels=True, third=False, counts=False, out_mem=None, cap=None, **kw):
+        """pcl::ISSKeypoint3D on the device (wm_iss_keypoints) -> dict: rc (WM_OK, or WM_ERR_ARG with more keypoints
+        than `cap`), indices (the keypoints' caller indices, ascending int32), labels (n,) uint8 WM_ISS_*, third (n,)
+        float64, counts (n,) int32 (n_s; -1 for a non-finite point) -- each None unless asked for -- n_out and the fields
+        of wm_iss_stats.  `cloud`: float32 (n, 3|4) numpy array or a torch tensor (n, >= 3) on the host or a HIP device.
+        out_mem: where the outputs are written; by default where the cloud lives.  `params`: an IssParams, a dict of
+        its fields, or None; keywords override fields (salient_radius and non_max_radius must be given).  cap: room for
+        the keypoints (default n)."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        if isinstance(params, IssParams):
+            params = {k: getattr(params, k) for k, _ in IssParams._fields_}
+        p = iss_params(params, **kw)
+        out_mem = mem if out_mem is None else out_mem
+        cap = n if cap is None else int(cap)
+        n_out = C.c_size_t(0)
+        st = IssStats()
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            idx = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            lab = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if labels else None
+            thr = torch.zeros(max(n, 1), dtype=torch.float64, device=dev) if third else None
+            cnt = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev) if counts else None
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+
+            def addr(a):
+                return C.c_void_p(a.data_ptr()) if a is not None else None
+        else:
+            idx = np.empty(max(cap, 1), np.int32)
+            lab = np.zeros(max(n, 1), np.uint8) if labels else None
+            thr = np.zeros(max(n, 1), np.float64) if third else None
+            cnt = np.full(max(n, 1), -1, np.int32) if counts else None
+
+            def addr(a):
+                return C.c_void_p(a.ctypes.data) if a is not None else None
+        rc = lib().wm_iss_keypoints(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), addr(idx), cap, out_mem,
+                                    C.byref(n_out), addr(lab), addr(thr), addr(cnt), C.byref(st))
+        if rc < 0 and not (rc == WM_ERR_ARG and n_out.value > cap):  # (more keypoints than cap: the caller's to handle)
+            self._check(rc, "wm_iss_keypoints")
+        out = dict(rc=rc, indices=idx[:min(n_out.value, cap)], labels=lab[:n] if labels else None,
+                   third=thr[:n] if third else None, counts=cnt[:n] if counts else None, n_out=n_out.value)
+        out.update({f: getattr(st, f) for f, _ in IssStats._fields_})
+        return out
+
+    def gather_records(self, src, idx):
+        """wm_gather_records: row idx[j] of `src` -> row j of the result.  src: a 2-D numpy array or torch tensor of a
+        4-byte type (contiguous rows: wm_fpfh_estimate's output); idx: int32 (m,) where src lives.  The result lives
+        there too.  An index outside the rows raises WmError."""
+        if isinstance(src, np.ndarray):
+            src = np.ascontiguousarray(src)
+            assert src.ndim == 2 and src.dtype.itemsize == 4
+            pi, m, keep_i = _index_arg(idx, WM_MEM_HOST)
+            dst = np.zeros((m, src.shape[1]), src.dtype)
+            ps, pd, mem = src.ctypes.data, dst.ctypes.data, WM_MEM_HOST
+        else:
+            import torch
+            assert isinstance(src, torch.Tensor) and src.dim() == 2 and src.element_size() == 4
+            src = src.contiguous()
+            mem = WM_MEM_DEVICE if src.is_cuda else WM_MEM_HOST
+            pi, m, keep_i = _index_arg(idx if mem == WM_MEM_DEVICE or isinstance(idx, np.ndarray) else idx.numpy(), mem)
+            dst = torch.zeros((m, src.shape[1]), dtype=src.dtype, device=src.device)
+            if mem == WM_MEM_DEVICE:
+                torch.cuda.synchronize(src.device)  # (the library works on a stream of its own)
+            ps, pd = src.data_ptr(), dst.data_ptr()
+        self._check(lib().wm_gather_records(self._h, C.c_void_p(ps), src.shape[0], src.shape[1] * 4, C.c_void_p(pi), m,
+                                            C.c_void_p(pd), mem), "wm_gather_records")
+        return dst
 
     # ---- NDT
     def ndt_align(self, params=None, **kw):

@@ -318,6 +318,8 @@ struct wm_ctx {
     int tune_sac_round = 256;    // stream entries a round of the RANSAC loop evaluates at the most (1 ... 1024)
     // pose from correspondences (wm_corr_ransac.hip)
     int tune_corr_round = 256;   // the same for the RANSAC over correspondences (1 ... 1024)
+    // keypoints (wm_iss.hip)
+    float tune_iss_cell_div = 2.f;  // the detector's grid cell is at least max(salient, non-max radius) / this (0.5 ... 8)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_grid_rows = 1;      // a grid level's counting sort by (y, z) rows: 1 where it pays (rows_apply, wm_grid.hip), 0 never, 2 wherever possible
@@ -356,6 +358,7 @@ struct wm_ctx {
     void *boxes = nullptr;                  // wm_describe.hip: the cluster boxes' workspace (its own as well)
     void *fpfh = nullptr;                   // wm_fpfh.hip, wm_feature_match.hip: the descriptors' workspace (its own as well)
     void *corr = nullptr;                   // wm_corr_ransac.hip: the workspace of the RANSAC over correspondences (its own as well)
+    void *iss = nullptr;                    // wm_iss.hip: the keypoint detector's workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -681,6 +684,9 @@ void fpfh_release(wm_ctx *ctx);
 
 // ---- wm_corr_ransac.hip
 void corr_release(wm_ctx *ctx);
+
+// ---- wm_iss.hip
+void iss_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0
