@@ -99,8 +99,14 @@ enum { /* pcl::registration::DefaultConvergenceCriteria::ConvergenceState */
        WM_CONV_REL_MSE = 4,
        WM_CONV_NO_CORRESPONDENCES = 5,
        WM_CONV_FORCED = 6,
-       /* WM_ICP_PLANE only (no PCL counterpart): J^T J of an iteration is singular to rounding -- the matched normals
-        * leave a motion free (one plane: three).  The align ends NOT converged, T_out untouched: loud, not wrong */
+       /* WM_ICP_PLANE and WM_ICP_GN6 (no PCL counterpart): J^T J of an iteration is singular to rounding.  PLANE: the
+        * matched normals leave a motion free (one plane: three).  GN6: the matched pairs do -- collinear pairs (a line
+        * against a line, three pairs in a row) the rotation about their line, coincident ones every rotation; a
+        * Cholesky pivot at or below 1e-12 of its own diagonal entry says so, on every path (wm_icp_align, wm_icp_match,
+        * wm_icp_batch_match, the sharded ones, wm_host_icp_apply; wm_gn6_from_stats returns WM_NOT_CONVERGED).  The
+        * align ends NOT converged, T_out untouched: loud, not wrong -- the step of such a system was measured to
+        * raise the residual by many orders of magnitude.  WM_ICP_SVD is well defined on the same input (any of the
+        * equally good rotations) and registers it */
        WM_CONV_DEGENERATE = 7 };
 /* Correspondence rejection between an iteration's search and its step (pcl::IterativeClosestPoint::
  * addCorrespondenceRejector with ONE rejector) [PCL-upstream: restated from PCL 1.8's registration/impl/icp.hpp,
@@ -127,8 +133,14 @@ typedef struct {
     double t_eps;         /* ICPMatcherParams::t_eps,    icp.hpp:41 -> icp.cpp:49 */
     double fit_eps;       /* ICPMatcherParams::fit_eps,  icp.hpp:43 -> icp.cpp:50 */
     int force_iterations; /* >0: run exactly this many iterations (bench; no stop tests) */
-    int mode;             /* WM_ICP_SVD: PCL's Umeyama step (parity default);
-                             WM_ICP_GN6: 6x6 J^T J / J^T r Gauss-Newton step;
+    int mode;             /* WM_ICP_SVD: PCL's Umeyama step (parity default).  Accuracy far from the origin: sigma is
+                             formed from RAW sums (Sqp / n - qm pm^T), which costs seven to eight digits 55 km out --
+                             measured there: one step within 2.3e-8 m of a centred long double Umeyama over the points
+                             of a 30 m cloud (1.6e-9 rad, which is 9e-5 m of the pose's translation); near the origin
+                             within 1e-13 m (tests/test_icp_stress_gpu.py);
+                             WM_ICP_GN6: 6x6 J^T J / J^T r Gauss-Newton step, the rotation linearised about the
+                             ORIGIN (far from it a first step overshoots by |dw|^2 |p| / 2); ends with
+                             WM_CONV_DEGENERATE where the pairs leave a motion free;
                              WM_ICP_PLANE: the same 6x6 step on the point-to-plane residual, with normals
                              of the target estimated on the device once per target (wm_estimate_normals);
                              the stopping rules and their MSE (mean point-to-point d^2) are unchanged.

@@ -608,7 +608,7 @@ struct IterEvents {
             stats->nn_launches += 1;
         }
         if (!sharded) return;
-        const int ran_ar = s.iter + (s.state == WM_CONV_NO_CORRESPONDENCES ? 1 : 0);
+        const int ran_ar = s.iter + (s.state == WM_CONV_NO_CORRESPONDENCES || s.state == WM_CONV_DEGENERATE ? 1 : 0);
         for (int it = 0; it < ran_ar; ++it) {
             const size_t k = (size_t) 5 * (size_t) max_it + 2 * (size_t) it;
             if (k + 1 >= ctx->ev_pool.size() || k + 1 >= ar) break;

@@ -118,13 +118,20 @@ __host__ __device__ inline void icp_apply_stats(IcpDevState *st, const double *s
 #ifdef __HIP_DEVICE_COMPILE__
     st->dbg[4] = clock64();
 #endif
+    bool solved = true;
     if (mode == WM_ICP_SVD)
         umeyama_from_stats(stats, Tk, st->svd_warm ? st->svd_v : nullptr);
     else
-        gn6_from_stats(stats, Tk);
+        solved = gn6_from_stats(stats, Tk);
 #ifdef __HIP_DEVICE_COMPILE__
     st->dbg[5] = clock64();
 #endif
+    if (!solved) {  // J^T J singular to rounding (collinear or coincident pairs): no step -- the pose stays as it is
+        st->state = WM_CONV_DEGENERATE;
+        st->converged = 0;
+        st->done = 1;
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 16; ++k) Tc[k] = st->T[k];
     mat4_mul(Tk, Tc, Tn);

@@ -229,9 +229,11 @@ WM_HD void svd3(const double *A, double *U, double *S, double *V, const double *
 }
 
 // Cholesky solve of a symmetric positive definite system (compile-time indices).
-// returns false when A is not positive definite.
+// returns false when A is not positive definite -- or, with rel_tol > 0, when a pivot (what row i still holds once the
+// rows before it are eliminated) is not above rel_tol x A's OWN diagonal entry of that row: singular to rounding.  x is
+// then the solution of a system with that pivot replaced by 1: finite, and of no use.
 template <int N>
-WM_HD bool chol_solve(const double *A, const double *b, double *x) {
+WM_HD bool chol_solve(const double *A, const double *b, double *x, double rel_tol = 0.0) {
     double L[N * N];
     bool ok = true;
 #pragma unroll
@@ -244,7 +246,7 @@ WM_HD bool chol_solve(const double *A, const double *b, double *x) {
             for (int k = 0; k < N; ++k)
                 if (k < j) s -= L[i * N + k] * L[j * N + k];
             if (i == j) {
-                if (!(s > 0.0)) {
+                if (!(s > 0.0) || (rel_tol > 0.0 && !(s > rel_tol * A[i * N + i]))) {
                     ok = false;
                     s = 1.0;
                 }
@@ -397,7 +399,19 @@ WM_HD void umeyama_from_stats(const double *st, double *T, double *Vwarm = nullp
     T[15] = 1;
 }
 
-// Gauss-Newton step: (J^T J) delta = -J^T r, T_k = [exp(dw) | dt].
+// J^T J of a Gauss-Newton step is singular when the matched pairs leave a motion free: collinear pairs (the rotation
+// about their line), coincident ones (every rotation about the point).  A Cholesky pivot at or below kGnPivotTol x its
+// OWN diagonal entry says so.  Own, not the largest: 55 km from the origin the rotation rows' diagonal (n |p|^2) is 3e7
+// times the translation rows' (n), and a well-spread cloud there has pivots of 1e-8 of their own entries.  Pivots of a
+// singular system sit at the rounding level of the elimination, measured below 1e-14 of their entries (float32
+// points that are collinear only up to their own rounding included); 1e-12 is a hundred times that and four digits below
+// the smallest regular pivot measured (tests/test_icp_reference_cpu.py prints both).  wm_plane.hip's kPlanePivotTol is the
+// same figure against the largest entry: whatever passes that test passes this one.
+constexpr double kGnPivotTol = 1e-12;
+
+// Gauss-Newton step: (J^T J) delta = -J^T r, T_k = [exp(dw) | dt].  false: J^T J is singular to rounding (above) -- T
+// is finite and must not be applied: on such systems the step was measured to RAISE the residual, by up to 1e13
+// (icp_apply_stats ends the registration with WM_CONV_DEGENERATE).
 WM_HD bool gn6_from_stats(const double *st, double *T) {
     double H[36], delta[6], rhs[6], R[9];
     {
@@ -414,7 +428,7 @@ WM_HD bool gn6_from_stats(const double *st, double *T) {
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) rhs[i] = -st[kGnG + i];
-    const bool ok = chol_solve<6>(H, rhs, delta);
+    const bool ok = chol_solve<6>(H, rhs, delta, kGnPivotTol);
     rodrigues(delta + 3, R);
     mat4_identity(T);
 #pragma unroll

@@ -158,8 +158,13 @@ static void rodrigues(const double w[3], double R[9]) {
 
 /* Gauss-Newton step on sum |p + dt + dw x p - q|^2 (left perturbation):
  * J = [I | -[p]x], (J^T J) delta = -J^T r.  north_star's literal "6x6" solver. */
-static void gn6_step(const float *p, const float *q, int n, double T[16]) {
-    double H[36] = {0}, g[6] = {0}, Hinv[36], delta[6], R[9];
+/* Returns 0 -- and leaves T alone -- when J^T J is singular to rounding: a Cholesky pivot (what row a still holds once
+ * the rows before it are eliminated) at or below 1e-12 of that row's own diagonal entry.  This is the product's rule
+ * (kGnPivotTol) RESTATED, on the same raw sums in double: it lets the two be compared state for state, and it cannot
+ * catch a wrong threshold.  What holds the figure is tests/test_icp_reference_cpu.py::test_gn6_pivots_leave_a_gap
+ * (regular systems no lower than 1e-8, singular ones no higher than 1e-14) and the residuals measured there. */
+static int gn6_step(const float *p, const float *q, int n, double T[16]) {
+    double H[36] = {0}, g[6] = {0}, Hinv[36], delta[6], R[9], L[36];
     int i, a, b;
     for (i = 0; i < n; ++i) {
         double px = p[3 * i], py = p[3 * i + 1], pz = p[3 * i + 2];
@@ -172,11 +177,52 @@ static void gn6_step(const float *p, const float *q, int n, double T[16]) {
                 for (c = 0; c < 3; ++c) H[a * 6 + b] += J[c][a] * J[c][b];
         }
     }
-    wmo_inverse(6, H, Hinv);
-    for (a = 0; a < 6; ++a) {
-        double s = 0;
-        for (b = 0; b < 6; ++b) s += Hinv[a * 6 + b] * g[b];
-        delta[a] = -s;
+    for (a = 0; a < 6; ++a)
+        for (b = 0; b <= a; ++b) {
+            double s = H[a * 6 + b];
+            int c;
+            for (c = 0; c < b; ++c) s -= L[a * 6 + c] * L[b * 6 + c];
+            if (a == b) {
+                if (!(s > 0.0) || !(s > 1e-12 * H[a * 6 + a])) return 0;
+                L[a * 6 + a] = sqrt(s);
+            } else {
+                L[a * 6 + b] = s / L[b * 6 + b];
+            }
+        }
+    /* The step itself from the equations about the pairs' centroid c: r + dt + dw x p = r + (dt + dw x c) + dw x (p - c),
+     * the same step from a 6x6 whose condition does not grow with the fourth power of the distance from the origin
+     * (55 km out the raw system is beyond what an inverse in double can solve); sums in long double; dt = dt' - dw x c */
+    {
+        long double c[3] = {0, 0, 0}, Hl[36] = {0}, gl[6] = {0};
+        for (i = 0; i < n; ++i)
+            for (a = 0; a < 3; ++a) c[a] += p[3 * i + a];
+        for (a = 0; a < 3; ++a) c[a] /= n;
+        for (i = 0; i < n; ++i) {
+            long double px = p[3 * i] - c[0], py = p[3 * i + 1] - c[1], pz = p[3 * i + 2] - c[2];
+            long double r[3] = {(long double) p[3 * i] - q[3 * i], (long double) p[3 * i + 1] - q[3 * i + 1],
+                                (long double) p[3 * i + 2] - q[3 * i + 2]};
+            long double J[3][6] = {{1, 0, 0, 0, pz, -py}, {0, 1, 0, -pz, 0, px}, {0, 0, 1, py, -px, 0}};
+            int k;
+            for (a = 0; a < 6; ++a) {
+                for (k = 0; k < 3; ++k) gl[a] += J[k][a] * r[k];
+                for (b = 0; b < 6; ++b)
+                    for (k = 0; k < 3; ++k) Hl[a * 6 + b] += J[k][a] * J[k][b];
+            }
+        }
+        for (a = 0; a < 36; ++a) H[a] = (double) Hl[a];
+        for (a = 0; a < 6; ++a) g[a] = (double) gl[a];
+        wmo_inverse(6, H, Hinv);
+        for (a = 0; a < 6; ++a) {
+            double s = 0;
+            for (b = 0; b < 6; ++b) s += Hinv[a * 6 + b] * g[b];
+            delta[a] = -s;
+        }
+        {
+            long double w[3] = {delta[3], delta[4], delta[5]};
+            delta[0] = (double) (delta[0] - (w[1] * c[2] - w[2] * c[1]));
+            delta[1] = (double) (delta[1] - (w[2] * c[0] - w[0] * c[2]));
+            delta[2] = (double) (delta[2] - (w[0] * c[1] - w[1] * c[0]));
+        }
     }
     rodrigues(delta + 3, R);
     wmo_mat4_identity(T);
@@ -184,6 +230,7 @@ static void gn6_step(const float *p, const float *q, int n, double T[16]) {
         for (b = 0; b < 3; ++b) T[a * 4 + b] = R[a * 3 + b];
         T[a * 4 + 3] = delta[a];
     }
+    return 1;
 }
 
 int wmo_icp_align(const float *src, int n, const float *tgt, int m, const wmo_icp_params *p,
@@ -235,9 +282,13 @@ int wmo_icp_align(const float *src, int n, const float *tgt, int m, const wmo_ic
             converged = 0;
             break;
         }
-        if (p->mode == WMO_ICP_GN6)
-            gn6_step(pp, qq, n_corr, Tk);
-        else
+        if (p->mode == WMO_ICP_GN6) {
+            if (!gn6_step(pp, qq, n_corr, Tk)) {
+                state = WMO_CONV_DEGENERATE;
+                converged = 0;
+                break;
+            }
+        } else
             wmo_umeyama(pp, qq, n_corr, p->float_sums, Tk);
 
         if (p->incremental_float) {

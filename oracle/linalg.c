@@ -251,16 +251,9 @@ void wmo_svd_solve(int n, const double *A, const double *b, double *x) {
 /* From the 17 sufficient statistics to the rigid fit (Eigen::umeyama,
  * with_scaling=false): sigma = (1/n) sum (q-qm)(p-pm)^T, R = U S V^T,
  * S = diag(1,1,det(U)det(V)), t = qm - R pm.  p = src, q = dst. */
-void wmo_umeyama_from_stats(double n, const double sp[3], const double sq[3],
-                            const double sqp[9], double T[16]) {
-    double pm[3], qm[3], sigma[9], U[9], S[3], V[9], R[9];
+static void umeyama_from_sigma(const double sigma[9], const double pm[3], const double qm[3], double T[16]) {
+    double U[9], S[3], V[9], R[9];
     int i, j, k;
-    for (i = 0; i < 3; ++i) {
-        pm[i] = sp[i] / n;
-        qm[i] = sq[i] / n;
-    }
-    for (i = 0; i < 3; ++i)
-        for (j = 0; j < 3; ++j) sigma[i * 3 + j] = sqp[i * 3 + j] / n - qm[i] * pm[j];
     wmo_svd(3, sigma, U, S, V);
     {
         double d = wmo_det3(U) * wmo_det3(V);
@@ -278,6 +271,19 @@ void wmo_umeyama_from_stats(double n, const double sp[3], const double sq[3],
         T[i * 4 + 3] = qm[i] - (R[i * 3 + 0] * pm[0] + R[i * 3 + 1] * pm[1] + R[i * 3 + 2] * pm[2]);
     }
     T[15] = 1;
+}
+
+void wmo_umeyama_from_stats(double n, const double sp[3], const double sq[3],
+                            const double sqp[9], double T[16]) {
+    double pm[3], qm[3], sigma[9];
+    int i, j;
+    for (i = 0; i < 3; ++i) {
+        pm[i] = sp[i] / n;
+        qm[i] = sq[i] / n;
+    }
+    for (i = 0; i < 3; ++i)
+        for (j = 0; j < 3; ++j) sigma[i * 3 + j] = sqp[i * 3 + j] / n - qm[i] * pm[j];
+    umeyama_from_sigma(sigma, pm, qm, T);
 }
 
 /* Eigen::umeyama(src, dst, false) on n point pairs.  float_sums=1 mirrors
@@ -315,16 +321,31 @@ void wmo_umeyama(const float *src, const float *dst, int n, int float_sums, doub
                 sqp[a * 3 + b] = (double) sig[a * 3 + b] + (double) qm[a] * (double) pm[b] * n;
         wmo_umeyama_from_stats((double) n, sp, sq, sqp, T);
     } else {
-        double sp[3] = {0, 0, 0}, sq[3] = {0, 0, 0}, sqp[9] = {0};
-        for (i = 0; i < n; ++i) {
+        /* as Eigen does it: the means first, then sigma from the DEMEANED points -- in long double, so that a cloud
+         * tens of kilometres from the origin keeps its digits (raw sums of q p^T lose seven to eight there) */
+        long double pm[3] = {0, 0, 0}, qm[3] = {0, 0, 0}, sig[9] = {0};
+        double pmd[3], qmd[3], sigd[9];
+        for (i = 0; i < n; ++i)
             for (a = 0; a < 3; ++a) {
-                sp[a] += src[3 * i + a];
-                sq[a] += dst[3 * i + a];
+                pm[a] += src[3 * i + a];
+                qm[a] += dst[3 * i + a];
             }
-            for (a = 0; a < 3; ++a)
-                for (b = 0; b < 3; ++b) sqp[a * 3 + b] += (double) dst[3 * i + a] * (double) src[3 * i + b];
+        for (a = 0; a < 3; ++a) {
+            pm[a] /= n;
+            qm[a] /= n;
         }
-        wmo_umeyama_from_stats((double) n, sp, sq, sqp, T);
+        for (i = 0; i < n; ++i)
+            for (a = 0; a < 3; ++a)
+                for (b = 0; b < 3; ++b) sig[a * 3 + b] += (dst[3 * i + a] - qm[a]) * (src[3 * i + b] - pm[b]);
+        for (a = 0; a < 3; ++a) {
+            pmd[a] = (double) pm[a];
+            qmd[a] = (double) qm[a];
+        }
+        for (a = 0; a < 9; ++a) sigd[a] = (double) (sig[a] / n);
+        umeyama_from_sigma(sigd, pmd, qmd, T);
+        /* t = qm - R pm from the unrounded means */
+        for (a = 0; a < 3; ++a)
+            T[a * 4 + 3] = (double) (qm[a] - (T[a * 4 + 0] * pm[0] + T[a * 4 + 1] * pm[1] + T[a * 4 + 2] * pm[2]));
     }
 }
 

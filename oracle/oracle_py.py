@@ -68,7 +68,7 @@ class NdtResult(C.Structure):
 
 
 CONV_NAMES = {0: "NOT_CONVERGED", 1: "ITERATIONS", 2: "TRANSFORM", 3: "ABS_MSE", 4: "REL_MSE",
-              5: "NO_CORRESPONDENCES", 6: "FORCED"}
+              5: "NO_CORRESPONDENCES", 6: "FORCED", 7: "DEGENERATE"}
 
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)

@@ -75,7 +75,10 @@ enum {
     WMO_CONV_ABS_MSE = 3,
     WMO_CONV_REL_MSE = 4,
     WMO_CONV_NO_CORRESPONDENCES = 5,
-    WMO_CONV_FORCED = 6
+    WMO_CONV_FORCED = 6,
+    /* WMO_ICP_GN6: J^T J is singular to rounding (collinear or coincident pairs): no step, not converged, the pose as
+     * it was -- the product's WM_CONV_DEGENERATE, by the same rule stated on its own (gn6_step, icp.c) */
+    WMO_CONV_DEGENERATE = 7
 };
 
 typedef struct {

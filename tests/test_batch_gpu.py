@@ -83,7 +83,7 @@ def test_batch_edge_cases(wm, ctx, oracle):
     assert got[2]["rc"] == 0 and got[2]["iterations"] == want["iterations"]
     dt, ang = pose_error(got[2]["T"], want["T"])
     assert dt <= 1e-6 and ang <= 1e-6
-    assert got[3]["rc"] in (0, wm.WM_NOT_CONVERGED)                             # degenerate: must not hang
+    assert got[3]["rc"] == wm.WM_OK     # degenerate (sigma = 0): the identity, as the one-pair path and the oracle give
     assert got[4]["rc"] == wm.WM_TOO_FEW and got[5]["rc"] == wm.WM_TOO_FEW
     assert got[6]["rc"] == wm.WM_TOO_FEW                        # < 3 correspondences (PCL)
 
