@@ -17,6 +17,8 @@ template <typename PointT>
 FPFHEstimation<PointT>::FPFHEstimation(const FPFHEstimation &other)
     : input_{other.input_},
       params{other.params},
+      k_set{other.k_set},
+      normal_k_set{other.normal_k_set},
       normals_{other.normals_},
       normals_n{other.normals_n},
       normals_stride{other.normals_stride},
@@ -28,6 +30,8 @@ FPFHEstimation<PointT> &FPFHEstimation<PointT>::operator=(const FPFHEstimation &
     if (this != &other) {
         input_ = other.input_;
         params = other.params;
+        k_set = other.k_set;
+        normal_k_set = other.normal_k_set;
         normals_ = other.normals_;
         normals_n = other.normals_n;
         normals_stride = other.normals_stride;
@@ -49,7 +53,7 @@ void FPFHEstimation<PointT>::compute(std::vector<pcl::FPFHSignature33> &output) 
     if (!this->input_ || this->input_->points.empty()) return;
     const auto &in = *this->input_;
     if (!detail::fpfhCompute(this->ctx, this->device, in.points.data(), in.points.size(), sizeof(PointT), this->params,
-                             this->normals_, this->normals_n, this->normals_stride, output))
+                             this->k_set, this->normal_k_set, this->normals_, this->normals_n, this->normals_stride, output))
         output.clear();
 }
 

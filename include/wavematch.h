@@ -1233,6 +1233,91 @@ int wm_fpfh_estimate(wm_ctx *ctx, int which, const wm_fpfh_params *params /* NUL
                      const void *normals_in /* NULL ok */, float *fpfh_out, uint8_t *spfh_out /* NULL ok */, int out_mem,
                      wm_fpfh_stats *stats /* NULL ok */);
 
+/* Normals and descriptors over a RADIUS neighbourhood: pcl::NormalEstimation and pcl::FPFHEstimation with
+ * setRadiusSearch, cloud in and rows out (no wm_set_source / wm_set_target), as wm_iss_keypoints.
+ * [PCL-upstream: restated from PCL 1.8 features/impl/normal_3d.hpp, common/impl/centroid.hpp
+ * (computeMeanAndCovarianceMatrix), features/impl/fpfh.hpp; PCL is not linked; tests/fpfh_radius_reference.py is the
+ * checker.]  Float is float32, double is float64, every operation rounded and nothing fused.
+ *   neighbours   r2 = (float) (radius * radius), the product in double; r2 must be a normal float > 0.  A neighbour of
+ *                finite point i is a finite point j with d2(i, j) < r2 (strict), i itself included; d2 = (dx dx + dy dy)
+ *                + dz dz in float, the form every other call uses.  n_s: their number, i included.  A non-finite point
+ *                is nobody's neighbour.  r2 = m 2^x with m in [0.5, 1) (frexp), and e = ceil(x / 2).
+ *   normal       (viewpoint at the origin) for each neighbour j: d = p_j - p_i, three float subtractions, widened to
+ *                double.  Nine integer sums in int64, added exactly: the three first moments rint(d_c 2^(36 - e)) and the
+ *                six second moments xx xy xz yy yz zz, rint(d_a d_b 2^(36 - x)) -- the quantum of the keypoints' scatter
+ *                sums; rint rounds ties to even.  A term is below about 2^36 and n at most WM_ISS_MAX_POINTS (2^26): no
+ *                int64 overflows.  Then in double mean_c = S1_c 2^(e - 36) / n_s and C_ab = S2_ab 2^(x - 36) / n_s -
+ *                mean_a mean_b (the products as written: a power of two times the converted sum, divided by n_s), PCL's
+ *                single-pass computeMeanAndCovarianceMatrix.  From C to the record exactly as wm_estimate_normals: the
+ *                library's svd3 (IEEE operations only), the vector of the smallest value, normalised, negated when
+ *                n . p_i > 0, curvature S[2] / (S[0] + S[1] + S[2]); a largest value <= 0 gives (0, 0, 0, 0).  n_s < 3
+ *                gives (0, 0, 0, 0) (PCL: NaN).  wm_normal_from_sums is the step from the sums on, on the host.
+ *                DEVIATION: PCL adds doubles in its kd-tree's order; a set of integers has one sum.
+ *   SPFH(i)      over the neighbours j with 0 < d2 < r2 of the FEATURE radius (d2 == 0, the point itself or an exact
+ *                duplicate, is skipped in both passes, as in the k form): the pair features of the k form above, word
+ *                for word, with the point's own normal and the neighbour's.  Three histograms of 11 integer counts.
+ *                n_f: the number of such neighbours, skipped pairs included; a cloud with n_f > WM_FPFH_RADIUS_MAX_NEIGHBORS
+ *                (8191) at some point is outside the call's range.
+ *   FPFH(i)      for each such neighbour j: d2c = max(d2, r2 2^-16), ratio = r2 / d2c (a float division; in (1, 65536]),
+ *                W = (int64) rint((double) ratio 2^20); acc[b] += count_j[b] W in int64 over the 33 bins (counts <=
+ *                8191, neighbours <= 8191, W <= 2^36: acc < 2^62, and so is a block's total).  Per block total = sum_b
+ *                acc[b], exact; out[b] = (float) (((double) acc[b] * 100.0) / (double) total); total == 0 gives zeros.
+ *                A non-finite point and a point whose own normal is (0, 0, 0) give 33 zeros.  DEVIATIONS from PCL: the
+ *                weight is r2 / d2 instead of 1 / d2 (the common factor cancels in the normalisation), quantised to
+ *                2^-20 of the weakest weight; a neighbour nearer than r / 256 weighs as one at r / 256; the sum does not
+ *                depend on the order.
+ *   output       every output byte is a function of the inputs and the parameters: not of the grid's cell (option
+ *                "fpfh_cell_div", default 2, 0.5 ... 8: the cell is at least max(normal_radius, feature_radius) /
+ *                fpfh_cell_div), nor of the order of the points inside a cell; atan2f sees the same arguments whatever
+ *                the order. */
+#define WM_FPFH_RADIUS_MAX_NEIGHBORS 8191
+
+/* The normals of a cloud over `radius`.  The cloud (x y z first in each record) lives in `mem`; normals_out (n x 4
+ * floats: the unit normal and the curvature), counts_out (n: n_s, -1 for a non-finite point; NULL ok) and sums_out
+ * (n x 9 int64: the sums above, zeros for a non-finite point; for tests and developers; NULL ok) live in `out_mem`.
+ * Argument errors, found before a device is touched: a null ctx or normals_out; a null cloud with n > 0; a bad stride
+ * (< 12 or no multiple of 4), mem or out_mem; n above WM_ISS_MAX_POINTS; a radius that is not finite or whose float
+ * square is not a normal float > 0.  n == 0 is WM_OK with no device touched; a cloud without a finite point is WM_OK
+ * with zeros.  The workspace is the context's own (freed by wm_ctx_destroy); the registration state and every other
+ * workspace stay untouched.  The host waits once in the front (the cloud's box) and once behind the last kernel. */
+typedef struct {
+    size_t n_finite;
+    float kernel_ms;  /* the front to the last kernel */
+} wm_normals_radius_stats;
+int wm_normals_radius(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, double radius,
+                      float *normals_out, int32_t *counts_out /* NULL ok */, int64_t *sums_out /* NULL ok */, int out_mem,
+                      wm_normals_radius_stats *stats /* NULL ok */);
+
+/* The step from the nine sums to the record on the host (no device): sums, n_s, x (r2 = m 2^x, -125 <= x <= 128) and
+ * the point itself -> out[4].  WM_ERR_ARG: a null argument, a negative n_s, x out of range. */
+int wm_normal_from_sums(const int64_t sums[9], int n_s, int x, const float p[3], float out[4]);
+
+typedef struct {
+    double normal_radius;   /* read only when normals_in == NULL */
+    double feature_radius;
+} wm_fpfh_radius_params;
+typedef struct {
+    size_t n_finite;
+    size_t n_valid;        /* finite points whose own normal is not (0, 0, 0) */
+    size_t max_neighbors;  /* the largest n_f of the cloud */
+    float normals_ms;      /* device time of the normals (0 when given) */
+    float spfh_ms;         /* ... of the first walk: pair features and counts */
+    float weight_ms;       /* ... of the second walk: the weighted sums and their scaling */
+    float kernel_ms;       /* the front to the last kernel */
+} wm_fpfh_radius_stats;
+
+/* The descriptors of a cloud.  normals_in: NULL = the normals of wm_normals_radius at normal_radius; otherwise n x 4
+ * floats in `mem` in the cloud's order (the fourth is not read): PCL's setInputNormals.  fpfh_out: n x 33 floats;
+ * spfh_out (NULL ok): n x 33 uint16, the first walk's counts; counts_out (NULL ok): n entries, n_f, -1 for a non-finite
+ * point; all in `out_mem`.  Argument errors as wm_normals_radius (a null params or fpfh_out; feature_radius, and
+ * normal_radius when it is read, as `radius` there); n == 0 and a cloud without a finite point likewise.  A point with
+ * more than WM_FPFH_RADIUS_MAX_NEIGHBORS feature neighbours: counted on the device and brought back in the call's one
+ * final fetch, the call returns WM_ERR_ARG with stats->max_neighbors the true maximum; the outputs are unspecified; no
+ * kernel reads or writes out of range because of it. */
+int wm_fpfh_radius(wm_ctx *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, const wm_fpfh_radius_params *params,
+                   const void *normals_in /* NULL ok */, float *fpfh_out, uint16_t *spfh_out /* NULL ok */,
+                   int32_t *counts_out /* NULL ok */, int out_mem, wm_fpfh_radius_stats *stats /* NULL ok */);
+
 #define WM_FEATURE_DIM 33
 #define WM_FEATURE_MAX_ROWS (1u << 20)
 typedef struct {

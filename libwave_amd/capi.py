@@ -256,6 +256,23 @@ WM_GATHER_MAX_STRIDE = 65536  # bytes of a gather_records record
 assert C.sizeof(IssParams) == 40 and C.sizeof(IssStats) == 32
 
 
+class NormalsRadiusStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("kernel_ms", C.c_float)]
+
+
+class FpfhRadiusParams(C.Structure):
+    _fields_ = [("normal_radius", C.c_double), ("feature_radius", C.c_double)]
+
+
+class FpfhRadiusStats(C.Structure):
+    _fields_ = [("n_finite", C.c_size_t), ("n_valid", C.c_size_t), ("max_neighbors", C.c_size_t), ("normals_ms", C.c_float),
+                ("spfh_ms", C.c_float), ("weight_ms", C.c_float), ("kernel_ms", C.c_float)]
+
+
+WM_FPFH_RADIUS_MAX_NEIGHBORS = 8191  # feature neighbours of a point of a fpfh_radius call
+assert C.sizeof(NormalsRadiusStats) == 16 and C.sizeof(FpfhRadiusParams) == 16 and C.sizeof(FpfhRadiusStats) == 40
+
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -456,6 +473,11 @@ def lib():
         L.wm_iss_third.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(IssParams), _dp]
         L.wm_gather_records.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_int]
+        L.wm_normals_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NormalsRadiusStats)]
+        L.wm_normal_from_sums.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int, _fp, _fp]
+        L.wm_fpfh_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(FpfhRadiusParams),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(FpfhRadiusStats)]
         _LIB = L
     return _LIB
 
@@ -661,6 +683,18 @@ def iss_third(sums, n_s, x, params=None, **kw):
     if rc != WM_OK:
         raise WmError("wm_iss_third: %s" % lib().wm_strerror(rc).decode())
     return out.value
+
+
+def normal_from_sums(sums, n_s, x, p):
+    """wm_normal_from_sums, the step of wm_normals_radius from a point's nine integer sums (x y z, xx xy xz yy yz zz) on
+    the host (no device): the sums, the neighbour count, x (r2 = m 2^x) and the point itself -> (4,) float32."""
+    s = (C.c_int64 * 9)(*[int(v) for v in sums])
+    pt = np.ascontiguousarray(np.asarray(p, np.float32)[:3])
+    out = np.zeros(4, np.float32)
+    rc = lib().wm_normal_from_sums(s, int(n_s), int(x), pt.ctypes.data_as(_fp), out.ctypes.data_as(_fp))
+    if rc != WM_OK:
+        raise WmError("wm_normal_from_sums: %s" % lib().wm_strerror(rc).decode())
+    return out
 
 
 def _index_arg(a, mem):
@@ -1633,6 +1667,82 @@ class Context:
                    third=thr[:n] if third else None, counts=cnt[:n] if counts else None, n_out=n_out.value)
         out.update({f: getattr(st, f) for f, _ in IssStats._fields_})
         return out
+
+    def _radius_outputs(self, cloud, n, mem, out_mem, specs):
+        """the output arrays of a radius call, (name, columns, dtype name, fill) each or None -> (arrays, addr)"""
+        if out_mem == WM_MEM_DEVICE:
+            import torch
+            dev = cloud.device if mem == WM_MEM_DEVICE else "cuda:%d" % self.device
+            def make(sp):
+                a = torch.zeros((max(n, 1), sp[1]) if sp[1] else (max(n, 1),), dtype=getattr(torch, sp[2]), device=dev)
+                return a + sp[3] if sp[3] else a
+
+            arrs = [None if sp is None else make(sp) for sp in specs]
+            torch.cuda.synchronize(dev)  # (the library works on a stream of its own)
+            return arrs, (lambda a: C.c_void_p(a.data_ptr()) if a is not None else None)
+        arrs = [None if sp is None else np.full((max(n, 1), sp[1]) if sp[1] else (max(n, 1),), sp[3], getattr(np, sp[2]))
+                for sp in specs]
+        return arrs, (lambda a: C.c_void_p(a.ctypes.data) if a is not None else None)
+
+    def normals_radius(self, cloud, radius, counts=False, sums=False, out_mem=None):
+        """pcl::NormalEstimation with setRadiusSearch (wm_normals_radius) on a cloud of its own -- no set_source /
+        set_target -> dict: rc, normals (n, 4) float32 (unit normal, curvature), counts (n,) int32 (n_s; -1 for a
+        non-finite point), sums (n, 9) int64 (the rule's integer sums) -- each None unless asked for -- and the fields
+        of wm_normals_radius_stats.  `cloud`: float32 (n, 3|4) numpy array or a torch tensor (n, >= 3) on the host or a
+        HIP device.  out_mem: where the outputs are written; by default where the cloud lives."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        out_mem = mem if out_mem is None else out_mem
+        st = NormalsRadiusStats()
+        (nrm, cnt, sm), addr = self._radius_outputs(cloud, n, mem, out_mem, [("normals", 4, "float32", 0),
+                                                                              ("counts", 0, "int32", -1) if counts else None,
+                                                                              ("sums", 9, "int64", 0) if sums else None])
+        rc = self._check(lib().wm_normals_radius(self._h, C.c_void_p(ptr), n, stride, mem, float(radius), addr(nrm), addr(cnt),
+                                                 addr(sm), out_mem, C.byref(st)), "wm_normals_radius")
+        out = dict(rc=rc, normals=nrm[:n], counts=cnt[:n] if counts else None, sums=sm[:n] if sums else None)
+        out.update({f: getattr(st, f) for f, _ in NormalsRadiusStats._fields_})
+        return out
+
+    def fpfh_radius(self, cloud, feature_radius, normal_radius=None, normals=None, counts=False, out=None, **kw):
+        """pcl::FPFHEstimation with setRadiusSearch (wm_fpfh_radius) on a cloud of its own -- no set_source / set_target
+        -> dict: rc (WM_OK, or WM_ERR_ARG when a point has more than WM_FPFH_RADIUS_MAX_NEIGHBORS feature neighbours:
+        max_neighbors says how many), fpfh (n, 33) float32 in the cloud's order, and with counts=True spfh (n, 33) uint16
+        (the first walk's counts) and counts (n,) int32 (feature neighbours; -1 for a non-finite point), else None; and
+        the fields of wm_fpfh_radius_stats.  normals: None (estimated over normal_radius, which must then be given) or
+        (n, 4) float32 where the cloud lives, PCL's setInputNormals.  out: a float32 CUDA tensor (n, 33) to fill on the
+        device; keyword out_mem: where the outputs go otherwise (by default where the cloud lives)."""
+        ptr, n, stride, mem, keep_alive = _cloud_arg(cloud)
+        out_mem = kw.pop("out_mem", None)
+        if kw:
+            raise TypeError("unexpected keywords: %s" % sorted(kw))
+        out_mem = (WM_MEM_DEVICE if out is not None else mem) if out_mem is None else out_mem
+        p = FpfhRadiusParams(float(normal_radius) if normal_radius is not None else 0.0, float(feature_radius))
+        st = FpfhRadiusStats()
+        nptr = None
+        if normals is not None:
+            if mem == WM_MEM_HOST:
+                normals = np.ascontiguousarray(normals if isinstance(normals, np.ndarray) else normals.numpy(), dtype=np.float32)
+                assert normals.shape == (n, 4)
+                nptr = C.c_void_p(normals.ctypes.data)
+            else:
+                assert normals.is_cuda and normals.element_size() == 4 and tuple(normals.shape) == (n, 4)
+                normals = normals.contiguous()
+                nptr = C.c_void_p(normals.data_ptr())
+        (res, sp, cnt), addr = self._radius_outputs(cloud, n, mem, out_mem, [("fpfh", 33, "float32", 0) if out is None else None,
+                                                                              ("spfh", 33, "uint16", 0) if counts else None,
+                                                                              ("counts", 0, "int32", -1) if counts else None])
+        if out is not None:
+            import torch
+            assert out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, WM_FEATURE_DIM) and out.dtype == torch.float32
+            torch.cuda.synchronize(out.device)
+            res = out
+        rc = lib().wm_fpfh_radius(self._h, C.c_void_p(ptr), n, stride, mem, C.byref(p), nptr, addr(res), addr(sp), addr(cnt),
+                                  out_mem, C.byref(st))
+        if rc < 0 and not (rc == WM_ERR_ARG and st.max_neighbors > WM_FPFH_RADIUS_MAX_NEIGHBORS):  # (the caller's to handle)
+            self._check(rc, "wm_fpfh_radius")
+        d = dict(rc=rc, fpfh=res if out is not None else res[:n], spfh=sp[:n] if counts else None,
+                 counts=cnt[:n] if counts else None)
+        d.update({f: getattr(st, f) for f, _ in FpfhRadiusStats._fields_})
+        return d
 
     def gather_records(self, src, idx):
         """wm_gather_records: row idx[j] of `src` -> row j of the result.  src: a 2-D numpy array or torch tensor of a

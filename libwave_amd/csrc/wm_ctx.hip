@@ -241,6 +241,8 @@ const Option kOptions[] = {
     {"corr_round", "WM_TUNE_CORR_ROUND", &wm_ctx::tune_corr_round, nullptr, 1, 1024, 0},
     // keypoints (wm_iss.hip)
     {"iss_cell_div", "WM_TUNE_ISS_CELL_DIV", nullptr, &wm_ctx::tune_iss_cell_div, 0.5, 8, 0},
+    // radius normals and descriptors (wm_fpfh_radius.hip)
+    {"fpfh_cell_div", "WM_TUNE_FPFH_CELL_DIV", nullptr, &wm_ctx::tune_fpfh_cell_div, 0.5, 8, 0},
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     {"radix_min", "WM_TUNE_RADIX_MIN", &wm_ctx::tune_radix_min, nullptr, kIntMin, kIntMax, 0},
     // the grids' counting sort (wm_grid.hip)
@@ -340,6 +342,7 @@ void wm_ctx_destroy(wm_ctx *ctx) {
     fpfh_release(ctx);
     corr_release(ctx);
     iss_release(ctx);
+    fpfh_radius_release(ctx);
     for (auto &l : ctx->levels) {
         l.pts.release();
         l.cell_start.release();

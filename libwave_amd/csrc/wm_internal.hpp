@@ -320,6 +320,8 @@ struct wm_ctx {
     int tune_corr_round = 256;   // the same for the RANSAC over correspondences (1 ... 1024)
     // keypoints (wm_iss.hip)
     float tune_iss_cell_div = 2.f;  // the detector's grid cell is at least max(salient, non-max radius) / this (0.5 ... 8)
+    // radius normals and descriptors (wm_fpfh_radius.hip)
+    float tune_fpfh_cell_div = 2.f;  // the call's grid cell is at least max(normal, feature radius) / this (0.5 ... 8)
     // sorting (wm_sort.hpp) and NDT (wm_ndt.hip)
     int tune_radix_min = 256 << 10;  // sorts of more items take the library's own radix sort, smaller ones rocPRIM's
     int tune_grid_rows = 1;      // a grid level's counting sort by (y, z) rows: 1 where it pays (rows_apply, wm_grid.hip), 0 never, 2 wherever possible
@@ -359,6 +361,7 @@ struct wm_ctx {
     void *fpfh = nullptr;                   // wm_fpfh.hip, wm_feature_match.hip: the descriptors' workspace (its own as well)
     void *corr = nullptr;                   // wm_corr_ransac.hip: the workspace of the RANSAC over correspondences (its own as well)
     void *iss = nullptr;                    // wm_iss.hip: the keypoint detector's workspace (its own as well)
+    void *fpfh_radius = nullptr;            // wm_fpfh_radius.hip: the radius normals' and descriptors' workspace (its own as well)
     wm::DevBuf phase_log;                   // developer: per-iteration phase cycle sums of the search kernel
     wm::DevBuf cost_log;                    // developer: per-query search cost of every iteration (wm_debug_cost_log)
     int cost_log_iter = 0, cost_log_cap = 0;
@@ -687,6 +690,9 @@ void corr_release(wm_ctx *ctx);
 
 // ---- wm_iss.hip
 void iss_release(wm_ctx *ctx);
+
+// ---- wm_fpfh_radius.hip
+void fpfh_radius_release(wm_ctx *ctx);
 
 // ---- wm_plane.hip: the point-to-plane metric (WM_ICP_PLANE)
 constexpr int kPlaneDefaultK = 20;  // neighbours of a normal when the caller says 0

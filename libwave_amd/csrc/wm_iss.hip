@@ -26,6 +26,7 @@
 //                ascending; the number of keypoints goes behind the salient count.
 //   the end      both counters come back in one copy, and the host waits once, behind it.
 #include "wm_iss_rule.hpp"
+#include "wm_iss_sums.hpp"
 #include "wm_radius_walk.hpp"
 
 #include <float.h>
@@ -40,19 +41,6 @@ namespace wm {
 namespace {
 
 constexpr int kIssBlock = 64;  // queries (threads) of a walk's workgroup: one wave, as k_outlier_radius
-
-// rint(v) + 2^52 + 2^51 for |v| < 2^51: at that magnitude a double's quantum is 1, so the ADDITION rounds v to the
-// nearest integer, ties to even -- exactly rint -- and the integer sits in the low bits of the pattern, two's
-// complement.  The patterns are added as they are; iss_unbias takes the constant out, once per sum.
-constexpr double kIssMagic = 6755399441055744.0;
-constexpr unsigned long long kIssMagicBits = 0x4338000000000000ull;
-
-__device__ __forceinline__ unsigned long long iss_term(double product, double scale) {
-    return (unsigned long long) __double_as_longlong(product * scale + kIssMagic);  // (the scaling is exact: a power of two)
-}
-__device__ __forceinline__ long long iss_unbias(unsigned long long s, unsigned n_s) {
-    return (long long) (s - (unsigned long long) n_s * kIssMagicBits);  // (modulo 2^64: the true sum fits)
-}
 
 // ------------------------------------------------------------------ the scatter sums
 // sums_g: plane c (0 ... 5: xx xy xz yy yz zz) holds nf entries in grid order.  A hit is d2 < r2s, the lane's own

@@ -13,6 +13,7 @@
 #include "wm_icp_step.hpp"
 #include "wm_bins.hpp"
 #include "wm_gicp_dev.hpp"
+#include "wm_normal_rule.hpp"
 #include "wm_pair_terms.hpp"
 
 #include <string.h>
@@ -76,16 +77,9 @@ __global__ void __launch_bounds__(kNrmBlock) __attribute__((amdgpu_waves_per_eu(
                     c[a * 3 + b] = c[a * 3 + b] / kk - s[a] * s[b];
                     c[b * 3 + a] = c[a * 3 + b];
                 }
-        double U[9], S[3], V[9];
-        svd3<false>(c, U, S, V);  // S descending: lambda2 = S[0], lambda0 = S[2]
-        if (S[0] > 0.0) {
-            double nx = V[2], ny = V[5], nz = V[8];
-            const double inv = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
-            nx *= inv, ny *= inv, nz *= inv;
-            // pcl::flipNormalTowardsViewpoint, viewpoint at the origin: n . (0 - p) >= 0
-            if (nx * (double) q.x + ny * (double) q.y + nz * (double) q.z > 0.0) nx = -nx, ny = -ny, nz = -nz;
-            res = make_float4((float) nx, (float) ny, (float) nz, (float) (S[2] / (S[0] + S[1] + S[2])));
-        }
+        float r[4];
+        normal_finish(c, q.x, q.y, q.z, r);  // (wm_normal_rule.hpp: the finish the radius form shares)
+        res = make_float4(r[0], r[1], r[2], r[3]);
     }
     out[slot] = res;
 }
